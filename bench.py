@@ -8,11 +8,19 @@ headline configuration b=1, seq=262144, h=32, d=128 non-causal
 bwd = 2.5x fwd, TFLOP/s/GPU = FLOPs / time / 1e12 / world_size.
 
 Usage (driver contract):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 N=1 runs the whole sequence on one GPU (one flash-tile kernel per step);
 N>1 is launched by the driver under torchrun (one rank per GPU, RCCL) and
 runs the ring with seq/N tokens per rank — total work fixed => strong
 scaling.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set up, W warmup and K
+timed forward steps, the optional output dump, the result line.  --full
+adds every other measurement (fwd+bwd leg, dominant-kernel roofline, ring
+overlap probe at N>1, CPU baseline); their keys are null in a plain run.
+--dump-outputs DIR writes what the last timed step returned as
+DIR/<name>.npy (float32).  Inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
 """
 
 import argparse
@@ -59,9 +67,15 @@ def parse_args():
                    help="ring the fp32 delta instead of o in backward")
     p.add_argument("--striped", action="store_true",
                    help="use the striped causal variant (OpBurstAttnStrip)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run the fwd+bwd leg, the kernel roofline, the "
+                        "ring overlap probe (N>1) and the CPU baseline")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full: skip the CPU baseline leg")
     p.add_argument("--no-bwd", action="store_true",
-                   help="skip the fwd+bwd timing leg")
+                   help="with --full: skip the fwd+bwd timing leg")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs as DIR/<name>.npy")
     return p.parse_args()
 
 
@@ -94,15 +108,46 @@ def max_over_ranks(x):
     return float(t.item())
 
 
-def time_loop(fn, steps, warmup):
+def time_loop(fn, steps, warmup, keep=None):
+    """Mean seconds per step over `steps` timed calls (max over ranks).
+    With a `keep` list, the last timed call's return value is left in it."""
     for _ in range(warmup):
         fn()
     sync_all()
+    last = None
     t0 = time.perf_counter()
     for _ in range(steps):
-        fn()
+        last = None  # release the previous step's result before the next
+        last = fn()
     sync_all()
-    return max_over_ranks((time.perf_counter() - t0) / steps)
+    dt = (time.perf_counter() - t0) / steps
+    if keep is not None:
+        keep.append(last)
+    return max_over_ranks(dt)
+
+
+DUMP_BUDGET_BYTES = 32 << 20  # per run, all ranks together (cap: 64 MB)
+
+
+def dump_outputs(out_dir, named, rank, world):
+    """Write each tensor as <name>.npy (float32).  A tensor over its share
+    of the budget is reduced to a fixed, seeded sample of its rows (the
+    leading dims flattened, last dim kept), in ascending row order."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // (world * len(named))
+    for name, t in named.items():
+        t = t.detach()
+        rows = t.reshape(-1, t.shape[-1])
+        fit = max(1, share // (4 * rows.shape[1]))
+        if rows.shape[0] > fit:
+            g = torch.Generator(device="cpu").manual_seed(20240229)
+            idx = torch.randperm(rows.shape[0], generator=g)[:fit].sort().values
+            t = rows[idx.to(rows.device)]
+        fname = name if world == 1 else f"{name}_rank{rank}"
+        np.save(os.path.join(out_dir, fname + ".npy"),
+                t.float().cpu().numpy())
 
 
 def kernel_event_ms(ext, q, k, v, scale, causal, iters):
@@ -160,12 +205,14 @@ def main():
     ext = load_extension()
     scale = 1.0 / math.sqrt(args.dim)
 
-    g = torch.Generator(device="cpu").manual_seed(1234 + rank)
+    # seeded on the device: drawing ~1e9 normals per tensor on the host
+    # costs more than the timed steps of a plain run
+    g = torch.Generator(device=dev).manual_seed(1234 + rank)
     mk = lambda s: torch.randn(
-        args.batch, s, args.heads, args.dim, generator=g
-    ).to(dtype).to(dev)
+        args.batch, s, args.heads, args.dim, generator=g, device=dev
+    ).to(dtype)
     q, k, v = mk(s_local), mk(s_local), mk(s_local)
-    do = mk(s_local)
+    do = mk(s_local) if args.full and not args.no_bwd else None
     log(f"[bench] rank {rank}/{world} s_local={s_local} dtype={args.dtype}")
 
     causal = args.causal
@@ -173,7 +220,7 @@ def main():
 
     def fwd_step():
         with torch.no_grad():
-            attn(q, k, v, None, "cuda", causal)
+            return attn(q, k, v, None, "cuda", causal)
 
     def fwdbwd_step():
         qg = q.detach().requires_grad_()
@@ -182,8 +229,13 @@ def main():
         o = attn(qg, kg, vg, None, "cuda", causal, args.optimize_bwd_comm)
         torch.autograd.grad(o, (qg, kg, vg), do)
 
-    t_fwd = time_loop(fwd_step, args.steps, args.warmup)
-    t_fb = None if args.no_bwd else time_loop(fwdbwd_step, args.steps, args.warmup)
+    kept = []
+    t_fwd = time_loop(fwd_step, args.steps, args.warmup, keep=kept)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"o": kept[0]}, rank, world)
+    kept.clear()
+    t_fb = (time_loop(fwdbwd_step, args.steps, args.warmup)
+            if args.full and not args.no_bwd else None)
 
     flops_fwd = 4.0 * args.batch * args.seq**2 * args.heads * args.dim
     if causal:
@@ -193,7 +245,7 @@ def main():
 
     # roofline of the dominant kernel (local fwd tile), rank 0
     roofline = None
-    if rank == 0:
+    if args.full and rank == 0:
         kms = kernel_event_ms(ext, q, k, v, scale, causal, iters=3)
         # algorithmic flops of ONE launch: this rank's q rows vs its
         # current kv (per ring step per GPU)
@@ -230,7 +282,7 @@ def main():
     # comm time NOT hidden under the tile kernels (north_star: >=90%).
     ring_stats = None
     try:
-      if world > 1:
+      if args.full and world > 1:
         from burst_attn_amd.comm import Ring
         from burst_attn_amd.tile import get_tile_provider
 
@@ -267,7 +319,8 @@ def main():
         ring_stats = {"error": repr(e)}
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if (args.full and rank == 0 and world == 1
+            and not args.no_cpu_baseline):
         log("[bench] timing CPU baseline (oracle port) ...")
         cpu_baseline = cpu_baseline_leg(args, scale)
 

@@ -55,7 +55,7 @@ def load_reference_tile_math():
     return ns
 
 
-def gen_tile_fixture(ns, name, b, sq, sk, n, d, seed, rounds=2):
+def gen_tile_fixture(ns, name, b, sq, sk, n, d, seed, rounds=2, split_bwd=False):
     """Golden vectors for one tile shape.
 
     Replays the reference math path over ``rounds`` kv chunks with carry-in
@@ -94,8 +94,14 @@ def gen_tile_fixture(ns, name, b, sq, sk, n, d, seed, rounds=2):
         dq=dq, dk=dk, dv=dv,
         scale=np.float32(scale), rounds=np.int64(rounds),
     )
+    out = {k: (t.numpy() if torch.is_tensor(t) else t) for k, t in out.items()}
     path = os.path.join(GOLDEN_DIR, f"{name}.npz")
-    np.savez_compressed(path, **{k: (t.numpy() if torch.is_tensor(t) else t) for k, t in out.items()})
+    if split_bwd:
+        # two archives, each under the 1 MiB per-file limit: the backward
+        # half (do and the gradients) goes to bwd_<name>.npz
+        bwd = {k: out.pop(k) for k in ("do", "dq", "dk", "dv")}
+        np.savez_compressed(os.path.join(GOLDEN_DIR, f"bwd_{name}.npz"), **bwd)
+    np.savez_compressed(path, **out)
     print(f"wrote {path}: q{tuple(q.shape)} k{tuple(k_cat.shape)}")
 
 
@@ -122,10 +128,15 @@ def main():
     os.makedirs(GOLDEN_DIR, exist_ok=True)
     torch.set_num_threads(max(1, os.cpu_count() or 1))
     ns = load_reference_tile_math()
-    # d=64 and d=128 tiles; square and half-kv (zigzag) shapes
-    gen_tile_fixture(ns, "tile_b1_s256_n4_d64", 1, 256, 256, 4, 64, seed=1234)
-    gen_tile_fixture(ns, "tile_b2_s192_n2_d128", 2, 192, 192, 2, 128, seed=4321)
-    gen_tile_fixture(ns, "tile_halfkv_b1_s256_n2_d128", 1, 256, 128, 2, 128, seed=7)
+    # d=64 and d=128 tiles; square and half-kv (zigzag) shapes.  Every file
+    # stays under 1 MiB (fp32 noise does not compress): the square shapes
+    # are small — the oracle's default 512-row blocks never split these or
+    # the earlier 192..256-row ones, so nothing is lost — and the half-kv
+    # tile keeps its 256-row shape with its backward half in a second file.
+    gen_tile_fixture(ns, "tile_b1_s80_n3_d64", 1, 80, 80, 3, 64, seed=1234)
+    gen_tile_fixture(ns, "tile_b2_s36_n2_d128", 2, 36, 36, 2, 128, seed=4321)
+    gen_tile_fixture(ns, "tile_halfkv_b1_s256_n2_d128", 1, 256, 128, 2, 128,
+                     seed=7, split_bwd=True)
     gen_merge_fixture(ns, "merge_b1_s128_n4_d64", 1, 128, 4, 64, seed=99)
     gen_merge_fixture(ns, "merge_b2_s96_n2_d128", 2, 96, 2, 128, seed=100)
 

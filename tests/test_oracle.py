@@ -48,7 +48,11 @@ def test_tile_fwd_matches_reference_golden(path):
 
 @pytest.mark.parametrize("path", _tile_fixtures())
 def test_tile_bwd_matches_reference_golden(path):
-    z = np.load(path)
+    z = dict(np.load(path))
+    # a fixture too large for one file keeps do/dq/dk/dv in bwd_<name>.npz
+    bwd = os.path.join(os.path.dirname(path), "bwd_" + os.path.basename(path))
+    if os.path.exists(bwd):
+        z.update(np.load(bwd))
     to_flash = lambda a: torch.from_numpy(a).permute(0, 2, 1, 3).contiguous()
     q, k, v, do, o = (
         to_flash(z["q"]), to_flash(z["k"]), to_flash(z["v"]),

@@ -106,8 +106,10 @@ def test_world_size_one_no_comm():
 import os, sys, torch
 import torch.distributed as dist
 sys.path.insert(0, os.getcwd())
-os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-os.environ.setdefault("MASTER_PORT", "29599")
+# own rendezvous: a parent that already opened a process group exports its
+# MASTER_PORT, and that port is still bound while the parent lives
+os.environ["MASTER_ADDR"] = "127.0.0.1"
+os.environ["MASTER_PORT"] = "29599"
 dist.init_process_group("gloo", rank=0, world_size=1)
 from burst_attn_amd.tile import _set_tile_provider_for_testing
 from burst_attn_amd import burst_attn_func

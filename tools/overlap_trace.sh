@@ -3,8 +3,8 @@
 # (north_star: >=90% of each ring step's K/V transfer hidden under the
 # local tile kernel).  Two independent measurements:
 #
-# 1. bench.py's built-in probe (runs unattended in any N>1 launch,
-#    incl. the round-end driver's 1/2/4/8 sweep): the printed JSON line
+# 1. bench.py's built-in probe (runs in any N>1 launch that passes
+#    --full, plain runs time the headline only): the printed JSON line
 #    carries `ring: {compute_only_ms, comm_only_ms, exposed_comm_ms,
 #    overlap_frac}` where exposed = full_step - compute_only and
 #    overlap_frac = 1 - exposed/comm_only.
@@ -17,13 +17,14 @@
 # Usage (8-GPU box):  bash tools/overlap_trace.sh 8
 set -e
 N=${1:-8}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-OUT=${GRAFT_REPO_ROOT:-/root/repo}/gpurun_out/overlap_n$N
+OUT=${OUT:-$ROOT/profile_out/overlap_n$N}  # profile_out/ is git-ignored
 mkdir -p "$OUT"
 rocprofv3 --kernel-trace --stats -d "$OUT" -o trace -- \
   python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" \
     --master-addr 127.0.0.1 --master-port 29555 \
-    ${GRAFT_REPO_ROOT:-/root/repo}/bench.py \
-    --gpus "$N" --steps 2 --warmup 1 --seq 262144 --no-cpu-baseline \
+    "$ROOT/bench.py" \
+    --gpus "$N" --steps 2 --warmup 1 --seq 262144 --full --no-cpu-baseline \
   | tee "$OUT/bench.json"
 echo "trace + bench line under $OUT; overlap_frac is in the JSON 'ring' key"
