@@ -49,13 +49,14 @@ def build(verbose=True, force=False):
         "-DNDEBUG",
     ]
     objs = []
-    hdr = os.path.join(CSRC, "attn_common.h")
     abihdr = os.path.join(PKG_DIR, "..", "include", "burst_attn_hip.h")
+    hdrs = [abihdr] + [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC))
+                       if h.endswith(".h")]
     for src in DEVICE_SOURCES:
         sp = os.path.join(CSRC, src)
         op = os.path.join(BUILD, src.replace(".hip", ".o"))
         objs.append(op)
-        if force or _newer(sp, op) or _newer(hdr, op) or _newer(abihdr, op):
+        if force or _newer(sp, op) or any(_newer(h, op) for h in hdrs):
             _run([HIPCC, *common, "-c", sp, "-o", op], verbose)
     for src in HOST_SOURCES:
         sp = os.path.join(CSRC, src)

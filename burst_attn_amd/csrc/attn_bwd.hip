@@ -11,8 +11,9 @@
 // in place (strided), which lets the ring layer accumulate across rounds
 // with no elementwise-add passes or per-round allocations.
 //
-// Two kernel plans behind bahip_attn_bwd:
-//   deterministic=1 (atomic-free, 8 tile GEMMs — flash-attn executes 5):
+// Kernel plans behind bahip_attn_bwd (selection: see launch_bwd; the
+// `deterministic` argument does not choose between them):
+//   default "split8" (atomic-free, 8 tile GEMMs — flash-attn executes 5):
 //     1. bwd_preprocess: delta = rowsum(o * do) fp32  (flash's preprocess)
 //     2. dq kernel  (8 waves, q-block resident, streams k/v):
 //          S^T = mfma(K,Q); dP^T = mfma(V,dO); dS^T in-lane;
@@ -20,7 +21,7 @@
 //     3. dkdv kernels (kv-block resident, streams q/do):
 //          MODE 0 (dV): S = mfma(Q,K^T); dV^T += mfma(dO^T, P)
 //          MODE 1 (dK): + dP = mfma(dO,V^T); dK^T += mfma(Q^T, dS)
-//   deterministic=0 (default, 6 tile GEMMs — the flash-attn plan):
+//   BA_BWD_FUSED=2 "atomic6" (6 tile GEMMs — the flash-attn plan):
 //     1. bwd_preprocess
 //     2. bwd_dkq kernel (kv-resident, FLIPPED orientation: S^T = mfma(K,Q)
 //        with kv on the MFMA row axis and q on the lane axis, so lse/delta
@@ -36,10 +37,7 @@
 // Operand scheme and LDS swizzle: see attn_common.h.
 
 #include "attn_common.h"
-#include "../../include/burst_attn_hip.h"
-
-#include <stdio.h>
-#include <stdlib.h>
+#include "attn_host.h"
 
 namespace {
 
@@ -995,21 +993,19 @@ extern "C" int bahip_attn_bwd_preprocess(
     const void* o, const void* dout, float* delta, int64_t B, int64_t S,
     int64_t N, int64_t D, const int64_t o_strides[3],
     const int64_t do_strides[3], int o_dtype, int do_dtype, void* stream) {
-  if (o_dtype != do_dtype) return 1003;
+  if (o_dtype != do_dtype)
+    return ba_fail(BAHIP_ERR_DTYPE_MISMATCH,
+                   "o / dout dtype mismatch (%d vs %d)", o_dtype, do_dtype);
   dim3 grid((unsigned)((S + 31) / 32), (unsigned)N, (unsigned)B);
-#define LAUNCH_PRE(T, DD)                                                   \
-  bwd_preprocess_kernel<T, DD><<<grid, 256, 0, (hipStream_t)stream>>>(      \
-      (const T*)o, (const T*)dout, delta, (int)S, (int)N, o_strides[0],     \
-      o_strides[1], o_strides[2], do_strides[0], do_strides[1],             \
-      do_strides[2])
-  if (D == 128 && o_dtype == BAHIP_BF16) LAUNCH_PRE(__bf16, 128);
-  else if (D == 128 && o_dtype == BAHIP_F16) LAUNCH_PRE(_Float16, 128);
-  else if (D == 64 && o_dtype == BAHIP_BF16) LAUNCH_PRE(__bf16, 64);
-  else if (D == 64 && o_dtype == BAHIP_F16) LAUNCH_PRE(_Float16, 64);
-  else return 1002;
-#undef LAUNCH_PRE
-  BA_CHECK_LAUNCH();
-  return 0;
+  return ba_dispatch_td(D, o_dtype, [&](auto td) {
+    using T = typename decltype(td)::type;
+    bwd_preprocess_kernel<T, decltype(td)::D>
+        <<<grid, 256, 0, (hipStream_t)stream>>>(
+            (const T*)o, (const T*)dout, delta, (int)S, (int)N, o_strides[0],
+            o_strides[1], o_strides[2], do_strides[0], do_strides[1],
+            do_strides[2]);
+    return ba_launch_status();
+  });
 }
 
 // plan selection (all plans accumulate into dq/dk/dv; plans 0 and 1 are
@@ -1041,12 +1037,9 @@ static int launch_bwd(const void* dout, const void* q, const void* k,
                       const int64_t* dvs, float scale, int causal,
                       int deterministic, void* stream) {
   // read per call (cheap at one bwd invocation) so tests can flip plans
-  const char* ef = getenv("BA_BWD_FUSED");
-  const int env_fused = ef ? atoi(ef) : -1;
-  const char* df = getenv("BA_BWD_DK_FLIP");
-  const int dk_flip = df ? atoi(df) : 0;
-  const char* dbg = getenv("BA_DKQ_DBG");
-  const int dkq_dbg = dbg ? atoi(dbg) : 0;
+  const int env_fused = ba_env_int("BA_BWD_FUSED", -1);
+  const int dk_flip = ba_env_int("BA_BWD_DK_FLIP", 0);
+  const int dkq_dbg = ba_env_int("BA_DKQ_DBG", 0);
   (void)deterministic;  // plans 0/1 are deterministic by construction
   const int plan = env_fused >= 0 ? env_fused : 0;
   dim3 grid_kv((unsigned)((Sk + 255) / 256), (unsigned)N, (unsigned)B);
@@ -1061,8 +1054,7 @@ static int launch_bwd(const void* dout, const void* q, const void* k,
       ls[1], dqs[0], dqs[1], dqs[2], dks[0], dks[1], dks[2], dvs[0], dvs[1],  \
       dvs[2], scale, causal
 
-  const char* dqp_e = getenv("BA_DQ_PIPE");
-  const int dqp = dqp_e ? atoi(dqp_e) : 0;
+  const int dqp = ba_env_int("BA_DQ_PIPE", 0);
   if (plan != 2) {
 #define DQ_ARGS                                                               \
   (const T*)dout, (const T*)q, (const T*)k, (const T*)v, delta, lse, dq,      \
@@ -1124,16 +1116,15 @@ extern "C" int bahip_attn_bwd(
     const int64_t dq_strides[3], const int64_t dk_strides[3],
     const int64_t dv_strides[3], float softmax_scale, int causal,
     int deterministic, int dtype, void* stream) {
-  if (causal && Sq != Sk) return 1001;
-#define LAUNCH_BWD(T, DD)                                                     \
-  launch_bwd<T, DD>(dout, q, k, v, delta, lse, dq, dk, dv, B, Sq, Sk, N,      \
-                    do_strides, q_strides, k_strides, v_strides,              \
-                    delta_strides, lse_strides, dq_strides, dk_strides,       \
-                    dv_strides, softmax_scale, causal, deterministic, stream)
-  if (D == 128 && dtype == BAHIP_BF16) return LAUNCH_BWD(__bf16, 128);
-  if (D == 128 && dtype == BAHIP_F16) return LAUNCH_BWD(_Float16, 128);
-  if (D == 64 && dtype == BAHIP_BF16) return LAUNCH_BWD(__bf16, 64);
-  if (D == 64 && dtype == BAHIP_F16) return LAUNCH_BWD(_Float16, 64);
-#undef LAUNCH_BWD
-  return 1002;
+  if (causal && Sq != Sk)
+    return ba_fail(BAHIP_ERR_CAUSAL_SHAPE,
+                   "causal tiles require Sq == Sk (%d vs %d)", (int)Sq,
+                   (int)Sk);
+  return ba_dispatch_td(D, dtype, [&](auto td) {
+    return launch_bwd<typename decltype(td)::type, decltype(td)::D>(
+        dout, q, k, v, delta, lse, dq, dk, dv, B, Sq, Sk, N, do_strides,
+        q_strides, k_strides, v_strides, delta_strides, lse_strides,
+        dq_strides, dk_strides, dv_strides, softmax_scale, causal,
+        deterministic, stream);
+  });
 }

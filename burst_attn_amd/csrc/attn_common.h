@@ -194,9 +194,3 @@ __device__ __forceinline__ void ba_st_tr16row(T* lds, int kv, int d0,
   *(u32x2_t*)((char*)lds + b0) = lohalf;
   *(u32x2_t*)((char*)lds + b1) = hihalf;
 }
-
-#define BA_CHECK_LAUNCH()                         \
-  do {                                            \
-    hipError_t e_ = hipGetLastError();            \
-    if (e_ != hipSuccess) return (int)e_;         \
-  } while (0)

@@ -22,10 +22,10 @@
 //   * epilogue: o = O^T / l (fp32 out), lse = ln2*(m2 + log2(l)).
 
 #include "attn_common.h"
-#include "../../include/burst_attn_hip.h"
+#include "attn_host.h"
+#include "fwd_variants.h"
 
-#include <stdio.h>
-#include <stdlib.h>
+#include <stddef.h>
 
 namespace {
 
@@ -780,260 +780,124 @@ __global__ void tr16_probe_kernel(int mode, int* out) {
 
 }  // namespace
 
-static thread_local char g_err[256] = "";
-extern "C" const char* bahip_last_error(void) { return g_err; }
+extern "C" const char* bahip_last_error(void) { return ba_g_err; }
 
-template <typename T, int D>
-static int launch_fwd(const void* q, const void* k, const void* v, float* o,
-                      float* lse, int64_t B, int64_t Sq, int64_t Sk, int64_t N,
-                      const int64_t* qs, const int64_t* ks, const int64_t* vs,
-                      float scale, int causal, void* stream) {
-  // read per call (getenv is ~ns against ms-scale launches) so tests can
-  // flip the variant paths in-process, like the backward plans do.
-  // defaults: V^T image (tr16 measured -3%), per-subtile softmax (+3%)
-  const char* e;
-  const int vpath = (e = getenv("BA_FWD_VPATH")) ? atoi(e) : 0;
-  const int subt = (e = getenv("BA_FWD_SUBT")) ? atoi(e) : 1;
-  const int ntw = (e = getenv("BA_FWD_NT")) ? atoi(e) : 512;
-  const int nbuf = (e = getenv("BA_FWD_NBUF")) ? atoi(e) : 2;
-  const int kreg = (e = getenv("BA_FWD_KREG")) ? atoi(e) : 0;
-  if (kreg == 1 || kreg == 2) {
-    dim3 gk((unsigned)((Sq + 255) / 256), (unsigned)N, (unsigned)B);
-    if (kreg == 1)
-      attn_fwd_kernel<T, D, 64, 0, 0, 1, 512, 2, 1>
-          <<<gk, dim3(512), 0, (hipStream_t)stream>>>(
-              (const T*)q, (const T*)k, (const T*)v, o, lse, (int)Sq,
-              (int)Sk, (int)N, qs[0], qs[1], qs[2], ks[0], ks[1], ks[2],
-              vs[0], vs[1], vs[2], scale, causal, nullptr, nullptr, nullptr,
-              0, 0, 0, 0, 0, 0);
-    else
-      attn_fwd_kernel<T, D, 64, 0, 0, 1, 512, 4, 2>
-          <<<gk, dim3(512), 0, (hipStream_t)stream>>>(
-              (const T*)q, (const T*)k, (const T*)v, o, lse, (int)Sq,
-              (int)Sk, (int)N, qs[0], qs[1], qs[2], ks[0], ks[1], ks[2],
-              vs[0], vs[1], vs[2], scale, causal, nullptr, nullptr, nullptr,
-              0, 0, 0, 0, 0, 0);
-    BA_CHECK_LAUNCH();
-    return 0;
-  }
-  if (subt == 3) {
-    attn_fwd_kernel<T, D, 64, 0, 0, 3, 256, 4>
-        <<<dim3((unsigned)((Sq + 127) / 128), (unsigned)N, (unsigned)B),
-           dim3(256), 0, (hipStream_t)stream>>>(
-            (const T*)q, (const T*)k, (const T*)v, o, lse, (int)Sq, (int)Sk,
-            (int)N, qs[0], qs[1], qs[2], ks[0], ks[1], ks[2], vs[0], vs[1],
-            vs[2], scale, causal, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0,
-            0);
-    BA_CHECK_LAUNCH();
-    return 0;
-  }
-  if (subt == 2) {
-    attn_fwd_kernel<T, D, 64, 0, 0, 2, 512, 4>
-        <<<dim3((unsigned)((Sq + 255) / 256), (unsigned)N, (unsigned)B),
-           dim3(512), 0, (hipStream_t)stream>>>(
-            (const T*)q, (const T*)k, (const T*)v, o, lse, (int)Sq, (int)Sk,
-            (int)N, qs[0], qs[1], qs[2], ks[0], ks[1], ks[2], vs[0], vs[1],
-            vs[2], scale, causal, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0,
-            0);
-    BA_CHECK_LAUNCH();
-    return 0;
-  }
-  if (nbuf == 4 && ntw == 512) {
-    if (vpath == 0)
-      attn_fwd_kernel<T, D, 64, 0, 0, 1, 512, 4>
-          <<<dim3((unsigned)((Sq + 255) / 256), (unsigned)N, (unsigned)B),
-             dim3(512), 0, (hipStream_t)stream>>>(
-              (const T*)q, (const T*)k, (const T*)v, o, lse, (int)Sq,
-              (int)Sk, (int)N, qs[0], qs[1], qs[2], ks[0], ks[1], ks[2],
-              vs[0], vs[1], vs[2], scale, causal, nullptr, nullptr, nullptr,
-              0, 0, 0, 0, 0, 0);
-    else
-      attn_fwd_kernel<T, D, 64, 0, 1, 1, 512, 4>
-          <<<dim3((unsigned)((Sq + 255) / 256), (unsigned)N, (unsigned)B),
-             dim3(512), 0, (hipStream_t)stream>>>(
-              (const T*)q, (const T*)k, (const T*)v, o, lse, (int)Sq,
-              (int)Sk, (int)N, qs[0], qs[1], qs[2], ks[0], ks[1], ks[2],
-              vs[0], vs[1], vs[2], scale, causal, nullptr, nullptr, nullptr,
-              0, 0, 0, 0, 0, 0);
-    BA_CHECK_LAUNCH();
-    return 0;
-  }
-#define FWD_LAUNCH(VP, ST, NTV)                                               \
-  attn_fwd_kernel<T, D, 64, 0, VP, ST, NTV>                                   \
-      <<<dim3((unsigned)((Sq + NTV / 2 - 1) / (NTV / 2)), (unsigned)N,        \
-              (unsigned)B),                                                   \
-         dim3(NTV), 0, (hipStream_t)stream>>>(                                \
-          (const T*)q, (const T*)k, (const T*)v, o, lse, (int)Sq, (int)Sk,    \
-          (int)N, qs[0], qs[1], qs[2], ks[0], ks[1], ks[2], vs[0], vs[1],     \
-          vs[2], scale, causal, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0)
-  if (ntw == 256) {
-    if (vpath == 0) FWD_LAUNCH(0, 1, 256);
-    else FWD_LAUNCH(1, 1, 256);
-  } else if (vpath == 0 && subt == 0) FWD_LAUNCH(0, 0, 512);
-  else if (vpath == 0 && subt == 1) FWD_LAUNCH(0, 1, 512);
-  else if (vpath == 1 && subt == 0) FWD_LAUNCH(1, 0, 512);
-  else FWD_LAUNCH(1, 1, 512);
-#undef FWD_LAUNCH
-  BA_CHECK_LAUNCH();
-  return 0;
+// ---- forward launch layer ---------------------------------------------
+// One field per attn_fwd_kernel parameter, in kernel order.  launch_fwd
+// expands it into the <<<>>> call; the module-launched path hands it to
+// the runtime as the packed kernarg buffer (explicit arguments only: the
+// HIP runtime appends the hidden ones itself — verified by tools/asm_probe).
+struct fwd_args {
+  const void *q, *k, *v;
+  float *o, *lse;
+  int Sq, Sk, N;
+  int64_t q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh;
+  float scale;
+  int causal;
+  float *st_acc, *st_m, *st_l;
+  int64_t a_sb, a_ss, a_sh, ml_sb, ml_sh;
+  int carry_in;
+};
+
+// explicit-kernarg segment size of a kernel, from its parameter types
+template <typename F>
+struct kernarg_size;
+template <typename... P>
+struct kernarg_size<void (*)(P...)> {
+  static constexpr size_t value = [] {
+    size_t off = 0;
+    ((off = (off + alignof(P) - 1) / alignof(P) * alignof(P) + sizeof(P)), ...);
+    return off;
+  }();
+};
+using production_kernel_t = decltype(&attn_fwd_kernel<
+    _Float16, 128, 64, 1, BA_FWD_PRODUCTION.vpath, BA_FWD_PRODUCTION.subt,
+    BA_FWD_PRODUCTION.nt, BA_FWD_PRODUCTION.nbuf, BA_FWD_PRODUCTION.kreg>);
+static_assert(offsetof(fwd_args, carry_in) + sizeof(int) ==
+                      kernarg_size<production_kernel_t>::value &&
+                  sizeof(fwd_args) ==
+                      (kernarg_size<production_kernel_t>::value + 7) / 8 * 8,
+              "fwd_args must mirror attn_fwd_kernel's parameter list");
+
+// wave w of a workgroup owns 32 q rows: NT threads cover NT/2 rows
+static dim3 fwd_grid(const fwd_args& a, int64_t B, int nt) {
+  return dim3((unsigned)((a.Sq + nt / 2 - 1) / (nt / 2)), (unsigned)a.N,
+              (unsigned)B);
 }
 
-template <typename T, int D>
-static int launch_fwd_accum(const void* q, const void* k, const void* v,
-                            int64_t B, int64_t Sq, int64_t Sk, int64_t N,
-                            const int64_t* qs, const int64_t* ks,
-                            const int64_t* vs, float scale, int causal,
-                            float* acc, float* m, float* l,
-                            const int64_t* as, const int64_t* mls,
-                            int carry_in, void* stream) {
-  static const int vpath = [] {
-    const char* e = getenv("BA_FWD_VPATH");
-    return e ? atoi(e) : 0;
-  }();
-  static const int subt = [] {
-    const char* e = getenv("BA_FWD_SUBT");
-    return e ? atoi(e) : 1;  // per-subtile softmax pipeline (+3% measured)
-  }();
-  static const int ntw = [] {
-    const char* e = getenv("BA_FWD_NT");
-    return e ? atoi(e) : 512;
-  }();
-  static const int nbuf = [] {
-    const char* e = getenv("BA_FWD_NBUF");
-    return e ? atoi(e) : 2;
-  }();
-  static const int kreg = [] {
-    const char* e = getenv("BA_FWD_KREG");
-    return e ? atoi(e) : 0;
-  }();
-  if (kreg == 1 || kreg == 2) {
-    dim3 gridk((unsigned)((Sq + 255) / 256), (unsigned)N, (unsigned)B);
-    if (kreg == 1)
-      attn_fwd_kernel<T, D, 64, 1, 0, 1, 512, 2, 1>
-          <<<gridk, dim3(512), 0, (hipStream_t)stream>>>(
-              (const T*)q, (const T*)k, (const T*)v, nullptr, nullptr,
-              (int)Sq, (int)Sk, (int)N, qs[0], qs[1], qs[2], ks[0], ks[1],
-              ks[2], vs[0], vs[1], vs[2], scale, causal, acc, m, l, as[0],
-              as[1], as[2], mls[0], mls[1], carry_in);
-    else
-      attn_fwd_kernel<T, D, 64, 1, 0, 1, 512, 4, 2>
-          <<<gridk, dim3(512), 0, (hipStream_t)stream>>>(
-              (const T*)q, (const T*)k, (const T*)v, nullptr, nullptr,
-              (int)Sq, (int)Sk, (int)N, qs[0], qs[1], qs[2], ks[0], ks[1],
-              ks[2], vs[0], vs[1], vs[2], scale, causal, acc, m, l, as[0],
-              as[1], as[2], mls[0], mls[1], carry_in);
-    BA_CHECK_LAUNCH();
-    return 0;
-  }
-  if (subt == 3) {
-    dim3 grid3((unsigned)((Sq + 127) / 128), (unsigned)N, (unsigned)B);
-    attn_fwd_kernel<T, D, 64, 1, 0, 3, 256, 4>
-        <<<grid3, dim3(256), 0, (hipStream_t)stream>>>(
-            (const T*)q, (const T*)k, (const T*)v, nullptr, nullptr, (int)Sq,
-            (int)Sk, (int)N, qs[0], qs[1], qs[2], ks[0], ks[1], ks[2], vs[0],
-            vs[1], vs[2], scale, causal, acc, m, l, as[0], as[1], as[2],
-            mls[0], mls[1], carry_in);
-    BA_CHECK_LAUNCH();
-    return 0;
-  }
-  if (subt == 2) {
-    dim3 grid2((unsigned)((Sq + 255) / 256), (unsigned)N, (unsigned)B);
-    attn_fwd_kernel<T, D, 64, 1, 0, 2, 512, 4>
-        <<<grid2, dim3(512), 0, (hipStream_t)stream>>>(
-            (const T*)q, (const T*)k, (const T*)v, nullptr, nullptr, (int)Sq,
-            (int)Sk, (int)N, qs[0], qs[1], qs[2], ks[0], ks[1], ks[2], vs[0],
-            vs[1], vs[2], scale, causal, acc, m, l, as[0], as[1], as[2],
-            mls[0], mls[1], carry_in);
-    BA_CHECK_LAUNCH();
-    return 0;
-  }
-  if (nbuf == 4 && ntw == 512) {
-    dim3 grid4((unsigned)((Sq + 255) / 256), (unsigned)N, (unsigned)B);
-    if (vpath == 0)
-      attn_fwd_kernel<T, D, 64, 1, 0, 1, 512, 4>
-          <<<grid4, dim3(512), 0, (hipStream_t)stream>>>(
-              (const T*)q, (const T*)k, (const T*)v, nullptr, nullptr,
-              (int)Sq, (int)Sk, (int)N, qs[0], qs[1], qs[2], ks[0], ks[1],
-              ks[2], vs[0], vs[1], vs[2], scale, causal, acc, m, l, as[0],
-              as[1], as[2], mls[0], mls[1], carry_in);
-    else
-      attn_fwd_kernel<T, D, 64, 1, 1, 1, 512, 4>
-          <<<grid4, dim3(512), 0, (hipStream_t)stream>>>(
-              (const T*)q, (const T*)k, (const T*)v, nullptr, nullptr,
-              (int)Sq, (int)Sk, (int)N, qs[0], qs[1], qs[2], ks[0], ks[1],
-              ks[2], vs[0], vs[1], vs[2], scale, causal, acc, m, l, as[0],
-              as[1], as[2], mls[0], mls[1], carry_in);
-    BA_CHECK_LAUNCH();
-    return 0;
-  }
-#define FWD_ALAUNCH(VP, ST, NTV)                                              \
-  attn_fwd_kernel<T, D, 64, 1, VP, ST, NTV>                                   \
-      <<<dim3((unsigned)((Sq + NTV / 2 - 1) / (NTV / 2)), (unsigned)N,        \
-              (unsigned)B),                                                   \
-         dim3(NTV), 0, (hipStream_t)stream>>>(                                \
-          (const T*)q, (const T*)k, (const T*)v, nullptr, nullptr, (int)Sq,   \
-          (int)Sk, (int)N, qs[0], qs[1], qs[2], ks[0], ks[1], ks[2], vs[0],   \
-          vs[1], vs[2], scale, causal, acc, m, l, as[0], as[1], as[2],        \
-          mls[0], mls[1], carry_in)
-  if (ntw == 256) {
-    if (vpath == 0) FWD_ALAUNCH(0, 1, 256);
-    else FWD_ALAUNCH(1, 1, 256);
-  } else if (vpath == 0 && subt == 0) FWD_ALAUNCH(0, 0, 512);
-  else if (vpath == 0 && subt == 1) FWD_ALAUNCH(0, 1, 512);
-  else if (vpath == 1 && subt == 0) FWD_ALAUNCH(1, 0, 512);
-  else FWD_ALAUNCH(1, 1, 512);
-#undef FWD_ALAUNCH
-  BA_CHECK_LAUNCH();
-  return 0;
+template <typename T, int D, int OUT_STATE, int VPATH, int SUBT, int NT,
+          int NBUF, int KREG>
+static void launch_fwd(const fwd_args& a, int64_t B, hipStream_t stream) {
+  attn_fwd_kernel<T, D, 64, OUT_STATE, VPATH, SUBT, NT, NBUF, KREG>
+      <<<fwd_grid(a, B, NT), dim3(NT), 0, stream>>>(
+          (const T*)a.q, (const T*)a.k, (const T*)a.v, a.o, a.lse, a.Sq, a.Sk,
+          a.N, a.q_sb, a.q_ss, a.q_sh, a.k_sb, a.k_ss, a.k_sh, a.v_sb, a.v_ss,
+          a.v_sh, a.scale, a.causal, a.st_acc, a.st_m, a.st_l, a.a_sb, a.a_ss,
+          a.a_sh, a.ml_sb, a.ml_sh, a.carry_in);
 }
 
-extern "C" int bahip_attn_fwd_accum(
-    const void* q, const void* k, const void* v, int64_t B, int64_t Sq,
-    int64_t Sk, int64_t N, int64_t D, const int64_t q_strides[3],
-    const int64_t k_strides[3], const int64_t v_strides[3],
-    float softmax_scale, int causal, int dtype, float* acc, float* m,
-    float* l, const int64_t acc_strides[3], const int64_t ml_strides[2],
-    int carry_in, void* stream) {
-  if (causal && Sq != Sk) return 1001;
-  if (D == 128 && dtype == BAHIP_BF16)
-    return launch_fwd_accum<__bf16, 128>(q, k, v, B, Sq, Sk, N, q_strides,
-                                         k_strides, v_strides, softmax_scale,
-                                         causal, acc, m, l, acc_strides,
-                                         ml_strides, carry_in, stream);
-  if (D == 128 && dtype == BAHIP_F16)
-    return launch_fwd_accum<_Float16, 128>(q, k, v, B, Sq, Sk, N, q_strides,
-                                           k_strides, v_strides, softmax_scale,
-                                           causal, acc, m, l, acc_strides,
-                                           ml_strides, carry_in, stream);
-  if (D == 64 && dtype == BAHIP_BF16)
-    return launch_fwd_accum<__bf16, 64>(q, k, v, B, Sq, Sk, N, q_strides,
-                                        k_strides, v_strides, softmax_scale,
-                                        causal, acc, m, l, acc_strides,
-                                        ml_strides, carry_in, stream);
-  if (D == 64 && dtype == BAHIP_F16)
-    return launch_fwd_accum<_Float16, 64>(q, k, v, B, Sq, Sk, N, q_strides,
-                                          k_strides, v_strides, softmax_scale,
-                                          causal, acc, m, l, acc_strides,
-                                          ml_strides, carry_in, stream);
-  return 1002;
-}
-
-extern "C" int bahip_attn_fwd_finalize(const float* acc, const float* m,
-                                       const float* l, void* o, float* lse,
-                                       int64_t B, int64_t S, int64_t N,
-                                       int64_t D, int dtype, void* stream) {
-  const int rows_per_block = (D == 64) ? 64 : 32;  // 4 waves x 64/(D/16)
-  dim3 grid((unsigned)((S + rows_per_block - 1) / rows_per_block), (unsigned)N,
-            (unsigned)B);
-#define LAUNCH_FIN(T, DD)                                                   attn_fwd_finalize_kernel<T, DD><<<grid, 256, 0, (hipStream_t)stream>>>(       acc, m, l, (T*)o, lse, (int)S, (int)N)
-  if (D == 128 && dtype == BAHIP_BF16) LAUNCH_FIN(__bf16, 128);
-  else if (D == 128 && dtype == BAHIP_F16) LAUNCH_FIN(_Float16, 128);
-  else if (D == 64 && dtype == BAHIP_BF16) LAUNCH_FIN(__bf16, 64);
-  else if (D == 64 && dtype == BAHIP_F16) LAUNCH_FIN(_Float16, 64);
-  else return 1002;
-#undef LAUNCH_FIN
-  BA_CHECK_LAUNCH();
-  return 0;
+// Shared body of the three forward entry points.  out_state = 0: the
+// stateless tile (o, lse; state pointers null).  out_state = 1: the
+// carry-in accumulator (o/lse null), launched through hip_function when
+// one is given, else through the variant the BA_FWD_* knobs select.
+static int fwd_entry(void* hip_function, int out_state, const void* q,
+                     const void* k, const void* v, float* o, float* lse,
+                     int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t D,
+                     const int64_t* qs, const int64_t* ks, const int64_t* vs,
+                     float scale, int causal, int dtype, float* acc, float* m,
+                     float* l, const int64_t* as, const int64_t* mls,
+                     int carry_in, void* stream) {
+  if (causal && Sq != Sk)
+    return ba_fail(BAHIP_ERR_CAUSAL_SHAPE,
+                   "causal tiles require Sq == Sk (%d vs %d)", (int)Sq,
+                   (int)Sk);
+  static const int64_t none[3] = {0, 0, 0};
+  if (!out_state) as = mls = none;
+  const fwd_args a = {q, k, v, o, lse, (int)Sq, (int)Sk, (int)N,
+                      qs[0], qs[1], qs[2], ks[0], ks[1], ks[2],
+                      vs[0], vs[1], vs[2], scale, causal, acc, m, l,
+                      as[0], as[1], as[2], mls[0], mls[1], carry_in};
+  if (hip_function) {
+    if (D != 128 || (dtype != BAHIP_F16 && dtype != BAHIP_BF16))
+      return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                     "module forward: unsupported head_dim %d / dtype %d",
+                     (int)D, dtype);
+    size_t size = sizeof a;
+    void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, (void*)&a,
+                   HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    const dim3 grid = fwd_grid(a, B, BA_FWD_PRODUCTION.nt);
+    hipError_t e = hipModuleLaunchKernel(
+        (hipFunction_t)hip_function, grid.x, grid.y, grid.z,
+        BA_FWD_PRODUCTION.nt, 1, 1, 0, (hipStream_t)stream, nullptr, cfg);
+    if (e != hipSuccess)
+      return ba_fail((int)e, "module forward launch failed: %s",
+                     hipGetErrorString(e));
+    return ba_ok();
+  }
+  ba_fwd_knobs kn;
+  kn.vpath = ba_env_int(BA_FWD_KNOB_SPECS[0].env, kn.vpath);
+  kn.subt = ba_env_int(BA_FWD_KNOB_SPECS[1].env, kn.subt);
+  kn.nt = ba_env_int(BA_FWD_KNOB_SPECS[2].env, kn.nt);
+  kn.nbuf = ba_env_int(BA_FWD_KNOB_SPECS[3].env, kn.nbuf);
+  kn.kreg = ba_env_int(BA_FWD_KNOB_SPECS[4].env, kn.kreg);
+  const ba_fwd_choice c = ba_fwd_select(kn);
+  if (c.bad_knob)
+    return ba_fail(BAHIP_ERR_BAD_KNOB, "%s=%d is not an accepted value",
+                   c.bad_knob, c.bad_value);
+  return ba_dispatch_td(D, dtype, [&](auto td) {
+    using T = typename decltype(td)::type;
+    constexpr int TD = decltype(td)::D;
+#define BA_FWD_CASE(VP, ST, NTV, NB, KR)                                   \
+  if (c.variant == ba_fwd_variant{VP, ST, NTV, NB, KR}) {                  \
+    if (out_state)                                                         \
+      launch_fwd<T, TD, 1, VP, ST, NTV, NB, KR>(a, B, (hipStream_t)stream); \
+    else                                                                   \
+      launch_fwd<T, TD, 0, VP, ST, NTV, NB, KR>(a, B, (hipStream_t)stream); \
+  }
+    BA_FWD_VARIANTS(BA_FWD_CASE)
+#undef BA_FWD_CASE
+    return ba_launch_status();
+  });
 }
 
 extern "C" int bahip_attn_fwd(const void* q, const void* k, const void* v,
@@ -1043,39 +907,56 @@ extern "C" int bahip_attn_fwd(const void* q, const void* k, const void* v,
                               const int64_t k_strides[3],
                               const int64_t v_strides[3], float softmax_scale,
                               int causal, int dtype, void* stream) {
-  if (causal && Sq != Sk) {
-    snprintf(g_err, sizeof g_err, "causal tiles require Sq == Sk (%d vs %d)",
-             (int)Sq, (int)Sk);
-    return 1001;
-  }
-  if (D == 128) {
-    if (dtype == BAHIP_BF16)
-      return launch_fwd<__bf16, 128>(q, k, v, o, lse, B, Sq, Sk, N, q_strides,
-                                     k_strides, v_strides, softmax_scale,
-                                     causal, stream);
-    if (dtype == BAHIP_F16)
-      return launch_fwd<_Float16, 128>(q, k, v, o, lse, B, Sq, Sk, N,
-                                       q_strides, k_strides, v_strides,
-                                       softmax_scale, causal, stream);
-  } else if (D == 64) {
-    if (dtype == BAHIP_BF16)
-      return launch_fwd<__bf16, 64>(q, k, v, o, lse, B, Sq, Sk, N, q_strides,
-                                    k_strides, v_strides, softmax_scale,
-                                    causal, stream);
-    if (dtype == BAHIP_F16)
-      return launch_fwd<_Float16, 64>(q, k, v, o, lse, B, Sq, Sk, N, q_strides,
-                                      k_strides, v_strides, softmax_scale,
-                                      causal, stream);
-  }
-  snprintf(g_err, sizeof g_err, "unsupported head_dim %d / dtype %d", (int)D,
-           dtype);
-  return 1002;
+  return fwd_entry(nullptr, 0, q, k, v, o, lse, B, Sq, Sk, N, D, q_strides,
+                   k_strides, v_strides, softmax_scale, causal, dtype, nullptr,
+                   nullptr, nullptr, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int bahip_attn_fwd_accum(
+    const void* q, const void* k, const void* v, int64_t B, int64_t Sq,
+    int64_t Sk, int64_t N, int64_t D, const int64_t q_strides[3],
+    const int64_t k_strides[3], const int64_t v_strides[3],
+    float softmax_scale, int causal, int dtype, float* acc, float* m,
+    float* l, const int64_t acc_strides[3], const int64_t ml_strides[2],
+    int carry_in, void* stream) {
+  return bahip_attn_fwd_accum_fn(nullptr, q, k, v, B, Sq, Sk, N, D, q_strides,
+                                 k_strides, v_strides, softmax_scale, causal,
+                                 dtype, acc, m, l, acc_strides, ml_strides,
+                                 carry_in, stream);
+}
+
+extern "C" int bahip_attn_fwd_accum_fn(
+    void* hip_function, const void* q, const void* k, const void* v,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    float* acc, float* m, float* l, const int64_t acc_strides[3],
+    const int64_t ml_strides[2], int carry_in, void* stream) {
+  return fwd_entry(hip_function, 1, q, k, v, nullptr, nullptr, B, Sq, Sk, N, D,
+                   q_strides, k_strides, v_strides, softmax_scale, causal,
+                   dtype, acc, m, l, acc_strides, ml_strides, carry_in,
+                   stream);
+}
+
+extern "C" int bahip_attn_fwd_finalize(const float* acc, const float* m,
+                                       const float* l, void* o, float* lse,
+                                       int64_t B, int64_t S, int64_t N,
+                                       int64_t D, int dtype, void* stream) {
+  const int rows_per_block = (D == 64) ? 64 : 32;  // 4 waves x 64/(D/16)
+  dim3 grid((unsigned)((S + rows_per_block - 1) / rows_per_block), (unsigned)N,
+            (unsigned)B);
+  return ba_dispatch_td(D, dtype, [&](auto td) {
+    using T = typename decltype(td)::type;
+    attn_fwd_finalize_kernel<T, decltype(td)::D>
+        <<<grid, 256, 0, (hipStream_t)stream>>>(acc, m, l, (T*)o, lse, (int)S,
+                                                (int)N);
+    return ba_launch_status();
+  });
 }
 
 extern "C" int bahip_tr16_probe(int mode, int* out, void* stream) {
   tr16_probe_kernel<<<1, 64, 0, (hipStream_t)stream>>>(mode, out);
-  BA_CHECK_LAUNCH();
-  return 0;
+  return ba_launch_status();
 }
 
 extern "C" int bahip_mfma_probe(const void* a, const void* b, float* d,
@@ -1086,6 +967,5 @@ extern "C" int bahip_mfma_probe(const void* a, const void* b, float* d,
   else
     mfma_probe_kernel<_Float16><<<1, 64, 0, (hipStream_t)stream>>>(
         (const _Float16*)a, (const _Float16*)b, d);
-  BA_CHECK_LAUNCH();
-  return 0;
+  return ba_launch_status();
 }

@@ -1,0 +1,65 @@
+// Host-side helpers shared by the C-ABI entry points in attn_fwd.hip and
+// attn_bwd.hip: the last-error message, env knobs, launch status, and the
+// (head_dim, dtype) -> <T, D> dispatch.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+
+#include "../../include/burst_attn_hip.h"
+
+// One message buffer for both translation units (C++17 inline variable);
+// bahip_last_error() in attn_fwd.hip returns it.
+inline thread_local char ba_g_err[256] = "";
+
+// Every nonzero return goes through ba_fail, every zero return through
+// ba_ok, so bahip_last_error() never reports an earlier call's message.
+__attribute__((format(printf, 2, 3))) inline int ba_fail(int code,
+                                                         const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(ba_g_err, sizeof ba_g_err, fmt, ap);
+  va_end(ap);
+  return code;
+}
+inline int ba_ok() {
+  ba_g_err[0] = '\0';
+  return 0;
+}
+
+// Knobs are read per call (getenv is ~ns against ms-scale launches) so
+// tests can flip variants and plans in-process.
+inline int ba_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
+// status of the launch(es) just issued
+inline int ba_launch_status() {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess)
+    return ba_fail((int)e, "kernel launch failed: %s", hipGetErrorString(e));
+  return ba_ok();
+}
+#define BA_CHECK_LAUNCH()                          \
+  do {                                             \
+    if (int rc_ = ba_launch_status()) return rc_;  \
+  } while (0)
+
+// f(ba_td<T, D>{}) for the supported (head_dim, dtype) pairs, else 1002.
+template <typename T, int D_>
+struct ba_td {
+  using type = T;
+  static constexpr int D = D_;
+};
+template <typename F>
+int ba_dispatch_td(int64_t D, int dtype, F&& f) {
+  if (D == 128 && dtype == BAHIP_BF16) return f(ba_td<__bf16, 128>{});
+  if (D == 128 && dtype == BAHIP_F16) return f(ba_td<_Float16, 128>{});
+  if (D == 64 && dtype == BAHIP_BF16) return f(ba_td<__bf16, 64>{});
+  if (D == 64 && dtype == BAHIP_F16) return f(ba_td<_Float16, 64>{});
+  return ba_fail(BAHIP_ERR_UNSUPPORTED, "unsupported head_dim %d / dtype %d",
+                 (int)D, dtype);
+}

@@ -32,17 +32,23 @@ void check_qkv(const at::Tensor& t, const char* name) {
               " head stride must be a multiple of 8 elements");
 }
 
-void fill_strides(const at::Tensor& t, int64_t s[3]) {
-  s[0] = t.stride(0);
-  s[1] = t.stride(1);
-  s[2] = t.stride(2);
-}
+// {batch, seq, head} element strides of a [B,S,N,D] tensor, as the C ABI
+// takes them
+struct Strides3 {
+  int64_t s[3];
+  explicit Strides3(const at::Tensor& t)
+      : s{t.stride(0), t.stride(1), t.stride(2)} {}
+  operator const int64_t*() const { return s; }
+};
 
-// cross-tensor consistency vs q: batch/heads/head_dim agree, k/v seqlens
-// agree, dtypes are equal — a mismatch must raise here, not read out of
-// bounds on device.
-void check_qkv_consistent(const at::Tensor& q, const at::Tensor& k,
-                          const at::Tensor& v) {
+// per-tensor layout plus cross-tensor consistency vs q: batch/heads/head_dim
+// agree, k/v seqlens agree, dtypes are equal — a mismatch must raise here,
+// not read out of bounds on device.
+void check_qkv3(const at::Tensor& q, const at::Tensor& k,
+                const at::Tensor& v) {
+  check_qkv(q, "q");
+  check_qkv(k, "k");
+  check_qkv(v, "v");
   TORCH_CHECK(k.size(0) == q.size(0) && v.size(0) == q.size(0),
               "batch mismatch");
   TORCH_CHECK(k.size(2) == q.size(2) && v.size(2) == q.size(2),
@@ -65,56 +71,53 @@ void check_qkv_consistent(const at::Tensor& q, const at::Tensor& k,
 std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k,
                                  const at::Tensor& v, double softmax_scale,
                                  bool causal) {
-  check_qkv(q, "q");
-  check_qkv(k, "k");
-  check_qkv(v, "v");
+  check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
-  check_qkv_consistent(q, k, v);
   auto o = at::empty({B, Sq, N, D}, q.options().dtype(at::kFloat));
   auto lse = at::empty({B, N, Sq}, q.options().dtype(at::kFloat));
-  int64_t qs[3], ks[3], vs[3];
-  fill_strides(q, qs);
-  fill_strides(k, ks);
-  fill_strides(v, vs);
   auto stream = at::hip::getCurrentHIPStream().stream();
   BA_CALL(bahip_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                          o.data_ptr<float>(), lse.data_ptr<float>(), B, Sq,
-                         Sk, N, D, qs, ks, vs, (float)softmax_scale,
-                         causal ? 1 : 0, dtype_code(q), stream));
+                         Sk, N, D, Strides3(q), Strides3(k), Strides3(v),
+                         (float)softmax_scale, causal ? 1 : 0, dtype_code(q),
+                         stream));
   return {o, lse};
 }
 
-void attn_fwd_accum(const at::Tensor& q, const at::Tensor& k,
+// Checks and stride extraction shared by attn_fwd_accum (asm_fn null: the
+// in-binary kernel the BA_FWD_* knobs select) and attn_fwd_accum_asm
+// (asm_fn: the hipModule-loaded kernel).
+void fwd_accum_call(void* asm_fn, const at::Tensor& q, const at::Tensor& k,
                     const at::Tensor& v, double softmax_scale, bool causal,
                     at::Tensor& acc, at::Tensor& m, at::Tensor& l,
                     bool carry_in) {
-  check_qkv(q, "q");
-  check_qkv(k, "k");
-  check_qkv(v, "v");
+  check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
-  check_qkv_consistent(q, k, v);
   TORCH_CHECK(acc.scalar_type() == at::kFloat && m.scalar_type() == at::kFloat
                   && l.scalar_type() == at::kFloat, "state must be fp32");
   TORCH_CHECK(acc.size(1) == Sq && m.size(2) == Sq && l.size(2) == Sq,
               "state rows must match q rows");
   TORCH_CHECK(acc.stride(3) == 1 && m.stride(2) == 1 && l.stride(2) == 1,
               "state innermost dims must be contiguous");
-  int64_t qs[3], ks[3], vs[3], as[3];
-  fill_strides(q, qs);
-  fill_strides(k, ks);
-  fill_strides(v, vs);
-  fill_strides(acc, as);
   int64_t mls[2] = {m.stride(0), m.stride(1)};
   TORCH_CHECK(l.stride(0) == mls[0] && l.stride(1) == mls[1],
               "m/l stride mismatch");
   auto stream = at::hip::getCurrentHIPStream().stream();
-  BA_CALL(bahip_attn_fwd_accum(
-      q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Sq, Sk, N, D, qs, ks, vs,
-      (float)softmax_scale, causal ? 1 : 0, dtype_code(q),
-      acc.data_ptr<float>(), m.data_ptr<float>(), l.data_ptr<float>(), as,
-      mls, carry_in ? 1 : 0, stream));
+  BA_CALL(bahip_attn_fwd_accum_fn(
+      asm_fn, q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Sq, Sk, N, D,
+      Strides3(q), Strides3(k), Strides3(v), (float)softmax_scale,
+      causal ? 1 : 0, dtype_code(q), acc.data_ptr<float>(),
+      m.data_ptr<float>(), l.data_ptr<float>(), Strides3(acc), mls,
+      carry_in ? 1 : 0, stream));
+}
+
+void attn_fwd_accum(const at::Tensor& q, const at::Tensor& k,
+                    const at::Tensor& v, double softmax_scale, bool causal,
+                    at::Tensor& acc, at::Tensor& m, at::Tensor& l,
+                    bool carry_in) {
+  fwd_accum_call(nullptr, q, k, v, softmax_scale, causal, acc, m, l, carry_in);
 }
 
 std::vector<at::Tensor> attn_fwd_finalize(const at::Tensor& acc,
@@ -148,14 +151,11 @@ at::Tensor attn_bwd_preprocess(const at::Tensor& o, const at::Tensor& dout,
   } else {
     delta = at::empty({B, N, S}, o.options().dtype(at::kFloat));
   }
-  int64_t os[3], gs[3];
-  fill_strides(o, os);
-  fill_strides(dout, gs);
   auto stream = at::hip::getCurrentHIPStream().stream();
   BA_CALL(bahip_attn_bwd_preprocess(o.data_ptr(), dout.data_ptr(),
-                                    delta.data_ptr<float>(), B, S, N, D, os,
-                                    gs, dtype_code(o), dtype_code(dout),
-                                    stream));
+                                    delta.data_ptr<float>(), B, S, N, D,
+                                    Strides3(o), Strides3(dout), dtype_code(o),
+                                    dtype_code(dout), stream));
   return delta;
 }
 
@@ -178,12 +178,9 @@ void attn_bwd_accum(const at::Tensor& dout, const at::Tensor& q,
                     double softmax_scale, bool causal, bool deterministic,
                     at::Tensor& dq, at::Tensor& dk, at::Tensor& dv) {
   check_qkv(dout, "dout");
-  check_qkv(q, "q");
-  check_qkv(k, "k");
-  check_qkv(v, "v");
+  check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
-  check_qkv_consistent(q, k, v);
   TORCH_CHECK(dout.size(0) == B && dout.size(1) == Sq && dout.size(2) == N &&
                   dout.size(3) == D,
               "dout/q shape mismatch");
@@ -198,14 +195,6 @@ void attn_bwd_accum(const at::Tensor& dout, const at::Tensor& q,
   check_grad_out(dq, q, "dq");
   check_grad_out(dk, k, "dk");
   check_grad_out(dv, v, "dv");
-  int64_t gs[3], qs[3], ks[3], vs[3], dqs[3], dks[3], dvs[3];
-  fill_strides(dout, gs);
-  fill_strides(q, qs);
-  fill_strides(k, ks);
-  fill_strides(v, vs);
-  fill_strides(dq, dqs);
-  fill_strides(dk, dks);
-  fill_strides(dv, dvs);
   int64_t ds[2] = {delta.stride(0), delta.stride(1)};
   int64_t ls[2] = {lse.stride(0), lse.stride(1)};
   auto stream = at::hip::getCurrentHIPStream().stream();
@@ -213,8 +202,9 @@ void attn_bwd_accum(const at::Tensor& dout, const at::Tensor& q,
                          v.data_ptr(), delta.data_ptr<float>(),
                          lse.data_ptr<float>(), dq.data_ptr<float>(),
                          dk.data_ptr<float>(), dv.data_ptr<float>(), B, Sq,
-                         Sk, N, D, gs, qs, ks, vs, ds, ls, dqs, dks, dvs,
-                         (float)softmax_scale, causal ? 1 : 0,
+                         Sk, N, D, Strides3(dout), Strides3(q), Strides3(k),
+                         Strides3(v), ds, ls, Strides3(dq), Strides3(dk),
+                         Strides3(dv), (float)softmax_scale, causal ? 1 : 0,
                          deterministic ? 1 : 0, dtype_code(q), stream));
 }
 
@@ -237,9 +227,8 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
 // ---- hipModule side-load of the .s-built forward (round-3 on-ramp) ---
 // attn_fwd_asm_load(path, symbol): load the hsaco once per process and
 // bind the accum-form kernel; attn_fwd_accum_asm(...): same contract as
-// attn_fwd_accum, dispatched through the module (kernargs packed to the
-// kernel's exact C++ parameter layout; the HIP runtime appends the
-// hidden arguments itself — verified by tools/asm_probe).
+// attn_fwd_accum, dispatched through the module by
+// bahip_attn_fwd_accum_fn (which packs the kernargs and derives the grid).
 namespace {
 hipModule_t g_asm_mod = nullptr;
 std::string g_asm_path;
@@ -268,44 +257,8 @@ void attn_fwd_accum_asm(const at::Tensor& q, const at::Tensor& k,
   const int dt = dtype_code(q);
   TORCH_CHECK(g_asm_fn[dt] != nullptr, "asm forward not loaded");
   TORCH_CHECK(q.size(3) == 128, "asm forward: D=128 variants only");
-  check_qkv(q, "q");
-  check_qkv(k, "k");
-  check_qkv(v, "v");
-  check_qkv_consistent(q, k, v);
-  const auto B = q.size(0), Sq = q.size(1), N = q.size(2);
-  const auto Sk = k.size(1);
-  // exact mirror of attn_fwd_kernel's parameter list
-  struct {
-    const void *q, *k, *v;
-    float *o, *lse;
-    int Sq, Sk, N;
-    int64_t qs0, qs1, qs2, ks0, ks1, ks2, vs0, vs1, vs2;
-    float scale;
-    int causal;
-    float *st_acc, *st_m, *st_l;
-    int64_t a_sb, a_ss, a_sh, ml_sb, ml_sh;
-    int carry_in;
-  } args = {
-      q.data_ptr(), k.data_ptr(), v.data_ptr(), nullptr, nullptr,
-      (int)Sq, (int)Sk, (int)N,
-      q.stride(0), q.stride(1), q.stride(2),
-      k.stride(0), k.stride(1), k.stride(2),
-      v.stride(0), v.stride(1), v.stride(2),
-      (float)softmax_scale, causal ? 1 : 0,
-      acc.data_ptr<float>(), m.data_ptr<float>(), l.data_ptr<float>(),
-      acc.stride(0), acc.stride(1), acc.stride(2),
-      m.stride(0), m.stride(1), carry_in ? 1 : 0,
-  };
-  size_t size = sizeof(args);
-  void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args,
-                 HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
-                 HIP_LAUNCH_PARAM_END};
-  auto stream = at::hip::getCurrentHIPStream().stream();
-  TORCH_CHECK(hipModuleLaunchKernel(
-                  g_asm_fn[dt], (unsigned)((Sq + 255) / 256), (unsigned)N,
-                  (unsigned)B, 512, 1, 1, 0, stream, nullptr,
-                  cfg) == hipSuccess,
-              "asm forward launch failed");
+  fwd_accum_call(g_asm_fn[dt], q, k, v, softmax_scale, causal, acc, m, l,
+                 carry_in);
 }
 }  // namespace
 

@@ -25,14 +25,18 @@
  *     (D contiguous): every call ADDS its tile contribution in place, so
  *     the ring layer accumulates rounds without elementwise-add passes.
  *     Pass zero-filled buffers for plain (non-accumulating) semantics.
- *   - deterministic != 0 selects the atomic-free two-pass-dq kernel plan
- *     (bitwise run-to-run identical); deterministic == 0 (default)
- *     selects the fused dK+dQ plan with flash-attn's atomic fp32 dq
- *     accumulation (2 fewer tile GEMMs).
+ *   - deterministic is accepted for call compatibility and does not
+ *     select a plan: the default plan ("split8": two-pass dq + split
+ *     dV/dK, atomic-free) and BA_BWD_FUSED=1 are bitwise run-to-run
+ *     identical by construction.  Only BA_BWD_FUSED=2, the flash-attn
+ *     style fused dK+dQ experiment with atomic fp32 dq, is not.
  *   - causal implies Sq == Sk (equal-length tiles; the ring's zigzag /
  *     striped bookkeeping reduces every other case to non-causal tiles).
  *   - stream is a hipStream_t.
- * Returns 0 on success; nonzero = error (message via bahip_last_error()).
+ * Returns 0 on success; nonzero = error.  Every nonzero return sets the
+ * calling thread's bahip_last_error() message and every success clears it.
+ * Codes: the BAHIP_ERR_* values below; any other nonzero value is the
+ * hipError_t of a failed kernel launch.
  */
 #pragma once
 #include <stdint.h>
@@ -43,6 +47,11 @@ extern "C" {
 
 #define BAHIP_F16 0
 #define BAHIP_BF16 1
+
+#define BAHIP_ERR_CAUSAL_SHAPE 1001   /* causal with Sq != Sk */
+#define BAHIP_ERR_UNSUPPORTED 1002    /* head_dim not 64/128, or dtype */
+#define BAHIP_ERR_DTYPE_MISMATCH 1003 /* o / dout dtypes differ */
+#define BAHIP_ERR_BAD_KNOB 1004       /* BA_FWD_* value outside its set */
 
 const char* bahip_last_error(void);
 
@@ -62,6 +71,20 @@ int bahip_attn_fwd(
  * exp2 domain), l fp32 [B,N,S] (running sum); acc strided {b,s,h}, m/l
  * strided {b,h} with contiguous seq.  carry_in=0 initialises the state. */
 int bahip_attn_fwd_accum(
+    const void* q, const void* k, const void* v,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    float* acc, float* m, float* l, const int64_t acc_strides[3],
+    const int64_t ml_strides[2], int carry_in, void* stream);
+
+/* bahip_attn_fwd_accum through a hipModule-loaded kernel: hip_function is
+ * a hipFunction_t for a code object of the production accum variant
+ * (D = 128, default BA_FWD_* knobs) for this dtype.  Same arguments and
+ * checks; the knobs are not consulted.  A null hip_function is
+ * bahip_attn_fwd_accum. */
+int bahip_attn_fwd_accum_fn(
+    void* hip_function,
     const void* q, const void* k, const void* v,
     int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t D,
     const int64_t q_strides[3], const int64_t k_strides[3],

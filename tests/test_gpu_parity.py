@@ -433,7 +433,7 @@ def test_fwd_shape_fuzz():
         ), f"case {i}: b={b} sq={sq} sk={sk} n={n} d={d} causal={causal}"
 
 
-def test_error_paths():
+def test_error_paths(monkeypatch):
     """The binding layer fails loudly on contract violations."""
     q = _rand(1, 128, 2, 128, torch.float16, 1)
     ext = _ext()
@@ -445,6 +445,22 @@ def test_error_paths():
     with pytest.raises(RuntimeError):  # fp32 inputs rejected
         f32 = torch.randn(1, 128, 2, 128).cuda()
         ext.attn_fwd(f32, f32, f32, 0.1, False)
+    # a knob value outside its accepted set names the knob, in both forms
+    acc = torch.empty(1, 128, 2, 128, dtype=torch.float32, device="cuda")
+    m = torch.empty(1, 2, 128, dtype=torch.float32, device="cuda")
+    l = torch.empty(1, 2, 128, dtype=torch.float32, device="cuda")
+    monkeypatch.setenv("BA_FWD_SUBT", "7")
+    with pytest.raises(RuntimeError, match="BA_FWD_SUBT=7"):
+        ext.attn_fwd(q, q, q, 0.1, False)
+    with pytest.raises(RuntimeError, match="BA_FWD_SUBT=7"):
+        ext.attn_fwd_accum(q, q, q, 0.1, False, acc, m, l, False)
+    monkeypatch.delenv("BA_FWD_SUBT")
+    # the previous failure left a causal-shape / bad-knob message behind:
+    # the accum form's unsupported-head-dim error must carry its own
+    with pytest.raises(RuntimeError, match="unsupported head_dim 96"):
+        acc96 = torch.empty(1, 128, 2, 96, dtype=torch.float32, device="cuda")
+        ext.attn_fwd_accum(bad, bad, bad, 0.1, False, acc96, m, l, False)
+    ext.attn_fwd(q, q, q, 0.1, False)  # and the knob is read per call
     # flash="math" layout is not supported at the API layer
     import torch.distributed as dist
 
@@ -528,18 +544,25 @@ def test_asm_module_fwd_parity(asm, dtype, monkeypatch):
         assert torch.equal(ta, tb)
 
 
-@pytest.mark.parametrize("knobs", [
+FWD_ALT_KNOBS = pytest.mark.parametrize("knobs", [
     {"BA_FWD_SUBT": "2", "BA_FWD_NBUF": "4"},   # T15 double-pipeline
     {"BA_FWD_SUBT": "3", "BA_FWD_NBUF": "4"},   # 3-stage 1-wave scaffold
     {"BA_FWD_NBUF": "4"},                        # 4-buffer staging
     {"BA_FWD_VPATH": "1"},                       # tr16 V path
     {"BA_FWD_SUBT": "0"},                        # joint softmax
-], ids=["subt2", "subt3", "nbuf4", "vpath1", "subt0"])
+    {"BA_FWD_KREG": "1"},                        # K straight to registers
+    {"BA_FWD_KREG": "2"},                        # K-fragment prefetch
+    {"BA_FWD_NT": "256"},                        # 4-wave workgroups
+], ids=["subt2", "subt3", "nbuf4", "vpath1", "subt0", "kreg1", "kreg2",
+        "nt256"])
+
+
+@FWD_ALT_KNOBS
 @pytest.mark.parametrize("causal", [False, True])
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
 def test_fwd_alt_paths_vs_default(knobs, causal, dtype, monkeypatch):
     """Every env-selectable forward variant must agree with the default
-    path (the launchers read the knobs per call, so this runs in-process
+    path (the launcher reads the knobs per call, so this runs in-process
     like the backward-plan test).  Ragged sizes included: the variants
     share masking/boundary code but differ in staging and softmax
     structure, where boundary bugs would hide."""
@@ -557,3 +580,42 @@ def test_fwd_alt_paths_vs_default(knobs, causal, dtype, monkeypatch):
             monkeypatch.delenv(key)
         torch.testing.assert_close(o_alt, o_ref, **TOL[dtype])
         torch.testing.assert_close(lse_alt, lse_ref, rtol=1e-3, atol=2e-2)
+
+
+def _carry_in_two_halves(q, k, v, scale, dtype):
+    """fresh accum on the first kv half, carry-in on the second, finalize."""
+    ext = _ext()
+    b, sq, n, d = q.shape
+    half = k.shape[1] // 2
+    acc = torch.empty(b, sq, n, d, dtype=torch.float32, device=q.device)
+    m = torch.empty(b, n, sq, dtype=torch.float32, device=q.device)
+    l = torch.empty(b, n, sq, dtype=torch.float32, device=q.device)
+    ext.attn_fwd_accum(q, k[:, :half], v[:, :half], scale, False, acc, m, l,
+                       False)
+    ext.attn_fwd_accum(q, k[:, half:], v[:, half:], scale, False, acc, m, l,
+                       True)
+    return ext.attn_fwd_finalize(acc, m, l, dtype)
+
+
+_CARRY_IN_DEFAULT = {}
+
+
+@FWD_ALT_KNOBS
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+def test_fwd_alt_paths_carry_in_vs_default(knobs, dtype, monkeypatch):
+    """The same knob sets through the carry-in kernel (OUT_STATE=1), the
+    form the ring runs: ragged s_q=744 against two 384-row kv halves, so
+    the second call merges into carried state across a ragged q tail."""
+    scale = 1.0 / math.sqrt(128)
+    if dtype not in _CARRY_IN_DEFAULT:
+        q = _rand(1, 744, 2, 128, dtype, 140)
+        k = _rand(1, 768, 2, 128, dtype, 141)
+        v = _rand(1, 768, 2, 128, dtype, 142)
+        _CARRY_IN_DEFAULT[dtype] = (
+            q, k, v, _carry_in_two_halves(q, k, v, scale, dtype))
+    q, k, v, (o_ref, lse_ref) = _CARRY_IN_DEFAULT[dtype]
+    for key, val in knobs.items():
+        monkeypatch.setenv(key, val)
+    o_alt, lse_alt = _carry_in_two_halves(q, k, v, scale, dtype)
+    torch.testing.assert_close(o_alt.float(), o_ref.float(), **TOL[dtype])
+    torch.testing.assert_close(lse_alt, lse_ref, rtol=1e-3, atol=2e-2)
