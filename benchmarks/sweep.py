@@ -8,6 +8,13 @@ Single node:
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 \
       benchmarks/sweep.py --configs ring          # 8-GPU ring rows
 
+Grouped-query attention:
+  python benchmarks/sweep.py --configs gqa --kv-heads 8
+runs, at s=65536, the equal-heads row, the --kv-heads row (same FLOPs,
+counted on the query heads; fewer K/V bytes) and the backward tile both
+as the in-kernel group loop and as the G-launch comparator.  --kv-heads
+also applies to the other burst configs.
+
 Row fields mirror the reference's results_torch.jsonl semantics.
 """
 
@@ -48,16 +55,18 @@ def timeit(fn, steps, warmup):
     return float(t.item())
 
 
-def bench_burst(args, b, s_global, n, d, causal, striped, opt_bwd, steps, warmup):
+def bench_burst(args, b, s_global, n, d, causal, striped, opt_bwd, steps, warmup,
+                nk=None):
     from burst_attn_amd import burst_attn_func, burst_attn_func_striped
 
     world = dist.get_world_size()
     rank = dist.get_rank()
     s_local = s_global // world
+    nk = n if nk is None else nk
     dtype = torch.float16 if args.dtype == "fp16" else torch.bfloat16
     g = torch.Generator().manual_seed(1000 + rank)
-    mk = lambda: torch.randn(b, s_local, n, d, generator=g).to(dtype).cuda()
-    q, k, v, do = mk(), mk(), mk(), mk()
+    mk = lambda h=n: torch.randn(b, s_local, h, d, generator=g).to(dtype).cuda()
+    q, k, v, do = mk(), mk(nk), mk(nk), mk()
     func = burst_attn_func_striped if striped else burst_attn_func
 
     def fwd():
@@ -74,13 +83,58 @@ def bench_burst(args, b, s_global, n, d, causal, striped, opt_bwd, steps, warmup
     f = flops_fwd(b, s_global, n, d, causal)
     return {
         "method": "burst_striped" if striped else "burst",
-        "b": b, "s": s_global, "n": n, "d": d,
+        "b": b, "s": s_global, "n": n, "nk": nk, "d": d,
         "causal": causal, "opt_bwd": opt_bwd, "wsize": world,
         "dtype": args.dtype,
         "fwd_ms": round(t_f * 1e3, 2),
         "fwd_tflops_per_gpu": round(f / t_f / 1e12 / world, 2),
         "fwdbwd_ms": round(t_fb * 1e3, 2),
         "fwdbwd_tflops_per_gpu": round(3.5 * f / t_fb / 1e12 / world, 2),
+    }
+
+
+def bench_bwd_tile(args, b, s, n, nk, d, causal, g_launch, steps, warmup):
+    """Backward tile alone (dq + dV + dK kernels, accumulating form).
+
+    g_launch=False: one call with Nk-head k/v — the in-kernel group loop.
+    g_launch=True: the comparator — the same tile as G = n // nk calls of
+    the equal-heads path on strided head views (q/do/dq ``[:, :, g::G]``,
+    delta/lse ``[:, g::G]``, the same dk/dv): K/V are re-loaded and dk/dv
+    read-modify-written G times."""
+    from burst_attn_amd._ext import load_extension
+
+    ext = load_extension()
+    G = n // nk
+    dtype = torch.float16 if args.dtype == "fp16" else torch.bfloat16
+    gen = torch.Generator().manual_seed(11)
+    mk = lambda h: torch.randn(b, s, h, d, generator=gen).to(dtype).cuda()
+    q, k, v, do = mk(n), mk(nk), mk(nk), mk(n)
+    scale = 1.0 / math.sqrt(d)
+    o, lse = ext.attn_fwd(q, k, v, scale, causal)
+    delta = ext.attn_bwd_preprocess(o.to(dtype), do)
+    del o
+    dq = torch.zeros(b, s, n, d, dtype=torch.float32, device="cuda")
+    dk = torch.zeros(b, s, nk, d, dtype=torch.float32, device="cuda")
+    dv = torch.zeros_like(dk)
+
+    def grouped():
+        ext.attn_bwd_accum(do, q, k, v, delta, lse, scale, causal, True,
+                           dq, dk, dv)
+
+    def launches():
+        for g in range(G):
+            ext.attn_bwd_accum(do[:, :, g::G], q[:, :, g::G], k, v,
+                               delta[:, g::G], lse[:, g::G], scale, causal,
+                               True, dq[:, :, g::G], dk, dv)
+
+    t = timeit(launches if g_launch else grouped, steps, warmup)
+    f = 2.5 * flops_fwd(b, s, n, d, causal)  # bwd = 3.5x - 1x fwd
+    return {
+        "method": "bwd_tile_g_launch" if g_launch else "bwd_tile_group_loop",
+        "b": b, "s": s, "n": n, "nk": nk, "d": d, "causal": causal,
+        "wsize": 1, "dtype": args.dtype,
+        "bwd_ms": round(t * 1e3, 2),
+        "bwd_tflops_per_gpu": round(f / t / 1e12, 2),
     }
 
 
@@ -150,13 +204,21 @@ def bench_ring_naive(args, b, s_global, n, d, steps, warmup):
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--configs",
-                   choices=["quick", "ring", "batch", "single", "naive"],
+                   choices=["quick", "ring", "batch", "single", "naive", "gqa"],
                    default="quick")
     p.add_argument("--steps", type=int, default=3)
     p.add_argument("--warmup", type=int, default=1)
     p.add_argument("--dtype", choices=["fp16", "bf16"], default="fp16")
     p.add_argument("--out", default="results_mi355x.jsonl")
+    p.add_argument("--heads", type=int, default=32)
+    p.add_argument("--kv-heads", type=int, default=None,
+                   help="K/V heads (default: equal to --heads)")
+    p.add_argument("--seq", type=int, default=65536,
+                   help="sequence length of the gqa config")
     args = p.parse_args()
+    nk = args.heads if args.kv_heads is None else args.kv_heads
+    if nk < 1 or args.heads % nk:
+        p.error(f"--heads {args.heads} must be a multiple of --kv-heads {nk}")
 
     world = int(os.environ.get("WORLD_SIZE", 1))
     if world > 1:
@@ -169,25 +231,25 @@ def main():
     rank = dist.get_rank()
 
     rows = []
-    n, d = 32, 128
+    n, d = args.heads, 128
     if args.configs == "quick":  # 1-GPU-friendly sweep
         for s in (16384, 32768, 65536):
             for causal in (False, True):
                 rows.append(bench_burst(args, 1, s, n, d, causal, False, causal,
-                                        args.steps, args.warmup))
+                                        args.steps, args.warmup, nk))
         if world == 1:
             rows.append(bench_single_flash(args, 1, 65536, n, d, False,
                                            args.steps, args.warmup))
     elif args.configs == "ring":  # the README seq sweep (per world size)
         for s in (65536, 131072, 262144, 524288):
             rows.append(bench_burst(args, 1, s, n, d, False, False, False,
-                                    args.steps, args.warmup))
+                                    args.steps, args.warmup, nk))
         rows.append(bench_burst(args, 1, 524288, n, d, True, False, True,
-                                args.steps, args.warmup))  # config 4
+                                args.steps, args.warmup, nk))  # config 4
     elif args.configs == "batch":  # README batch scaling at s=65536
         for b in (1, 2, 4, 8):
             rows.append(bench_burst(args, b, 65536, n, d, True, False, False,
-                                    args.steps, args.warmup))
+                                    args.steps, args.warmup, nk))
     elif args.configs == "single":
         for s in (65536, 131072, 262144):
             rows.append(bench_single_flash(args, 1, s, n, d, False,
@@ -200,6 +262,17 @@ def main():
             r = bench_burst(args, 1, s, n, d, False, False, False,
                             args.steps, args.warmup)
             rows.append(r)
+    elif args.configs == "gqa":  # equal-heads vs --kv-heads, and the
+        # backward tile as group loop vs G-launch comparator
+        for causal in (False, True):
+            for h in dict.fromkeys((n, nk)):
+                rows.append(bench_burst(args, 1, args.seq, n, d, causal, False,
+                                        causal, args.steps, args.warmup, h))
+            if world == 1:
+                for g_launch in (False, True):
+                    rows.append(bench_bwd_tile(args, 1, args.seq, n, nk, d,
+                                               causal, g_launch, args.steps,
+                                               args.warmup))
 
     if rank == 0:
         with open(args.out, "a") as f:

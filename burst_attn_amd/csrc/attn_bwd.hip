@@ -38,6 +38,7 @@
 
 #include "attn_common.h"
 #include "attn_host.h"
+#include "gqa_heads.h"
 
 namespace {
 
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
     const T* __restrict__ dout, const T* __restrict__ q,
     const T* __restrict__ k, const T* __restrict__ v,
     const float* __restrict__ delta, const float* __restrict__ lse,
-    float* __restrict__ dq, int Sq, int Sk, int N,
+    float* __restrict__ dq, int Sq, int Sk, int N, int G,
     int64_t g_sb, int64_t g_ss, int64_t g_sh,
     int64_t q_sb, int64_t q_ss, int64_t q_sh,
     int64_t k_sb, int64_t k_ss, int64_t k_sh,
@@ -114,8 +115,10 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
 
   const T* qp = q + b * q_sb + (int64_t)n * q_sh;
   const T* gp = dout + b * g_sb + (int64_t)n * g_sh;
-  const T* kp = k + b * k_sb + (int64_t)n * k_sh;
-  const T* vp = v + b * v_sb + (int64_t)n * v_sh;
+  // grouped-query heads: q head n reads KV head n / G (wave-uniform)
+  const int nkv = n / G;
+  const T* kp = k + b * k_sb + (int64_t)nkv * k_sh;
+  const T* vp = v + b * v_sb + (int64_t)nkv * v_sh;
 
   frag qf[D / 16], gf[DQP ? 1 : D / 16];
 #pragma unroll
@@ -293,13 +296,25 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
 // MODE: 0 = dV (dv^T += mfma(dO^T, P)); 1 = dK (dk^T += mfma(Q^T, dS));
 //       2 = fused dK+dV (both accumulators; 8-wave; may spill — A/B)
 // QBLK: streamed q-tile rows (128 for dV measured -8%: 27-VGPR spills).
-template <typename T, int D, int MODE, int QBLK = 64>
+// GQA: 0 = one q head per workgroup (blockIdx.y = q head = kv head; G is
+//   ignored) — the equal-heads kernel, unchanged.
+//   1 = grouped-query heads: blockIdx.y is the KV head and the workgroup
+//   streams the q/dO/lse/delta tiles of its G query heads
+//   (heads blockIdx.y*G .. +G-1) through the same double-buffered
+//   pipeline as ONE flattened (g, tile) stream: the prefetch of head
+//   g+1's first tile overlaps head g's last tile, K/V fragments and the
+//   accumulator stay resident, and the epilogue is still one
+//   read-add-write per kv row.  Summation order is fixed (g ascending,
+//   tiles ascending), so the result stays bitwise deterministic.  A
+//   template parameter rather than a runtime G = 1 so the equal-heads
+//   instantiation keeps its register allocation (the dK kernel is tight).
+template <typename T, int D, int MODE, int QBLK = 64, int GQA = 0>
 __global__ __launch_bounds__(512) void bwd_dkv_kernel(
     const T* __restrict__ dout, const T* __restrict__ q,
     const T* __restrict__ k, const T* __restrict__ v,
     const float* __restrict__ delta, const float* __restrict__ lse,
     float* __restrict__ dout_acc, float* __restrict__ dout_acc2,
-    int Sq, int Sk, int N,
+    int Sq, int Sk, int N, int G,
     int64_t g_sb, int64_t g_ss, int64_t g_sh,
     int64_t q_sb, int64_t q_ss, int64_t q_sh,
     int64_t k_sb, int64_t k_ss, int64_t k_sh,
@@ -345,10 +360,14 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
   const int kvb = blockIdx.x * 256 + wave * 32;
   const int kv_col = kvb + l31;
 
-  const T* qp = q + b * q_sb + (int64_t)n * q_sh;
-  const T* gp = dout + b * g_sb + (int64_t)n * g_sh;
-  const float* dp_ = delta + b * d_sb + n * d_sh;
-  const float* lp_ = lse + b * l_sb + n * l_sh;
+  // n is the kv head; the q-side pointers start at the group's first q
+  // head (n itself without GQA) and step by one head stride per g
+  const int n0 = GQA ? n * G : n;
+  const int ng = GQA ? G : 1;
+  const T* qp = q + b * q_sb + (int64_t)n0 * q_sh;
+  const T* gp = dout + b * g_sb + (int64_t)n0 * g_sh;
+  const float* dp_ = delta + b * d_sb + n0 * d_sh;
+  const float* lp_ = lse + b * l_sb + n0 * l_sh;
 
   // resident K (always, for S); resident V when dP is needed
   frag kf[D / 16], vf[MODE >= 1 ? D / 16 : 1];
@@ -388,9 +407,13 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
 
   // per-lane lse*log2e and delta for both subtiles of a tile (l2[qs] =
   // {lse2, delta}), loaded straight from global — clamped, branchless
-  auto issue_loads = [&](int tile, u32x4_t* qreg, u32x4_t* greg,
+  auto issue_loads = [&](int g, int tile, u32x4_t* qreg, u32x4_t* greg,
                          float2* l2) {
     const int q0 = tile * QBLK;
+    const T* qpg = GQA ? qp + (int64_t)g * q_sh : qp;
+    const T* gpg = GQA ? gp + (int64_t)g * g_sh : gp;
+    const float* lpg = GQA ? lp_ + (int64_t)g * l_sh : lp_;
+    const float* dpg = GQA ? dp_ + (int64_t)g * d_sh : dp_;
 #pragma unroll
     for (int c = 0; c < PT; ++c) {
       const int flat = tid + c * NT;
@@ -400,16 +423,16 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
       // they contribute garbage x 0 to the dV/dK contractions
       const int qg = q0 + row;
       const int qc = qg < Sq ? qg : (Sq - 1);
-      qreg[c] = *(const u32x4_t*)(qp + (int64_t)qc * q_ss + col8 * 8);
-      greg[c] = *(const u32x4_t*)(gp + (int64_t)qc * g_ss + col8 * 8);
+      qreg[c] = *(const u32x4_t*)(qpg + (int64_t)qc * q_ss + col8 * 8);
+      greg[c] = *(const u32x4_t*)(gpg + (int64_t)qc * g_ss + col8 * 8);
     }
 #pragma unroll
     for (int qs = 0; qs < QBLK / 32; ++qs) {
       const int qg = q0 + qs * 32 + l31;
       const int qc = qg < Sq ? qg : (Sq - 1);
       // clamped rows contaminate nothing: the q_g < Sq mask zeroes p/dS
-      l2[qs].x = lp_[qc] * BA_LOG2E;
-      l2[qs].y = (MODE >= 1) ? dp_[qc] : 0.f;
+      l2[qs].x = lpg[qc] * BA_LOG2E;
+      l2[qs].y = (MODE >= 1) ? dpg[qc] : 0.f;
     }
   };
   auto write_lds = [&](int buf, const u32x4_t* qreg, const u32x4_t* greg) {
@@ -435,20 +458,27 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
   float2 l2c[QBLK / 32];
   {
     u32x4_t qreg[PT], greg[PT];
-    issue_loads(t0, qreg, greg, l2c);
+    issue_loads(0, t0, qreg, greg, l2c);
     write_lds(0, qreg, greg);
     __syncthreads();
   }
   if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= 256)
     __builtin_amdgcn_s_setprio(1);  // T5 static form (younger half)
 
+  // one flattened (g, tile) stream: the tile after a head's last one is
+  // the next head's tile t0 (the causal t0 skip and the `active` test
+  // depend on the tile index only, so they apply per head unchanged).
+  // Without GQA ng == 1 folds this back to the single-head loop.
   int cur = 0;
+  for (int g = 0; g < ng; ++g)
   for (int t = t0; t < nt; ++t) {
     const int q0 = t * QBLK;
-    const bool has_next = (t + 1) < nt;
+    const bool last_t = (t + 1) >= nt;
+    const bool has_next = !last_t || (GQA && g + 1 < ng);
     u32x4_t qreg[PT], greg[PT];
     float2 l2n[QBLK / 32] = {};
-    if (has_next) issue_loads(t + 1, qreg, greg, l2n);
+    if (has_next)
+      issue_loads(last_t ? g + 1 : g, last_t ? t0 : t + 1, qreg, greg, l2n);
 
     const bool active = !causal || (q0 + QBLK - 1 >= kvb);
     if (active) {
@@ -1030,7 +1060,7 @@ template <typename T, int D>
 static int launch_bwd(const void* dout, const void* q, const void* k,
                       const void* v, const float* delta, const float* lse,
                       float* dq, float* dk, float* dv, int64_t B, int64_t Sq,
-                      int64_t Sk, int64_t N, const int64_t* gs,
+                      int64_t Sk, int64_t N, int64_t Nk, const int64_t* gs,
                       const int64_t* qs, const int64_t* ks, const int64_t* vs,
                       const int64_t* ds, const int64_t* ls,
                       const int64_t* dqs, const int64_t* dks,
@@ -1042,7 +1072,25 @@ static int launch_bwd(const void* dout, const void* q, const void* k,
   const int dkq_dbg = ba_env_int("BA_DKQ_DBG", 0);
   (void)deterministic;  // plans 0/1 are deterministic by construction
   const int plan = env_fused >= 0 ? env_fused : 0;
-  dim3 grid_kv((unsigned)((Sk + 255) / 256), (unsigned)N, (unsigned)B);
+  const int64_t G = ba_gqa_group(N, Nk);
+  if (!G)
+    return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                   "q heads N=%d must be a positive multiple of kv heads "
+                   "Nk=%d",
+                   (int)N, (int)Nk);
+  // the bwd_dkq_kernel experiment plans are equal-heads only
+  if (G > 1 && (plan == 1 || plan == 2))
+    return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                   "BA_BWD_FUSED=%d does not support grouped-query heads "
+                   "(N=%d, Nk=%d)",
+                   plan, (int)N, (int)Nk);
+  if (G > 1 && dk_flip)
+    return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                   "BA_BWD_DK_FLIP=%d does not support grouped-query heads "
+                   "(N=%d, Nk=%d)",
+                   dk_flip, (int)N, (int)Nk);
+  // kv-resident kernels: one workgroup column per KV head
+  dim3 grid_kv((unsigned)((Sk + 255) / 256), (unsigned)Nk, (unsigned)B);
   // head-first grid for the dkq/dkvf kernels
   dim3 grid_dkq((unsigned)N, (unsigned)((Sk + 255) / 256), (unsigned)B);
   dim3 grid_dq((unsigned)((Sq + 255) / 256), (unsigned)N, (unsigned)B);
@@ -1058,9 +1106,9 @@ static int launch_bwd(const void* dout, const void* q, const void* k,
   if (plan != 2) {
 #define DQ_ARGS                                                               \
   (const T*)dout, (const T*)q, (const T*)k, (const T*)v, delta, lse, dq,      \
-      (int)Sq, (int)Sk, (int)N, gs[0], gs[1], gs[2], qs[0], qs[1], qs[2],     \
-      ks[0], ks[1], ks[2], vs[0], vs[1], vs[2], ds[0], ds[1], ls[0], ls[1],   \
-      dqs[0], dqs[1], dqs[2], scale, causal
+      (int)Sq, (int)Sk, (int)N, (int)G, gs[0], gs[1], gs[2], qs[0], qs[1],    \
+      qs[2], ks[0], ks[1], ks[2], vs[0], vs[1], vs[2], ds[0], ds[1], ls[0],   \
+      ls[1], dqs[0], dqs[1], dqs[2], scale, causal
     if (dqp)
       bwd_dq_kernel<T, D, 1><<<grid_dq, 512, 0, (hipStream_t)stream>>>(DQ_ARGS);
     else
@@ -1074,11 +1122,19 @@ static int launch_bwd(const void* dout, const void* q, const void* k,
     BA_CHECK_LAUNCH();
     return 0;
   }
-  bwd_dkv_kernel<T, D, 0, 64><<<grid_kv, 512, 0, (hipStream_t)stream>>>(
-      (const T*)dout, (const T*)q, (const T*)k, (const T*)v, delta, lse, dv,
-      nullptr, (int)Sq, (int)Sk, (int)N, gs[0], gs[1], gs[2], qs[0], qs[1],
-      qs[2], ks[0], ks[1], ks[2], vs[0], vs[1], vs[2], ds[0], ds[1], ls[0],
-      ls[1], dvs[0], dvs[1], dvs[2], scale, causal);
+  // G = 1 runs the equal-heads instantiation (GQA = 0), G > 1 the
+  // group-loop one; OUT/OS = the accumulator and its strides
+#define DKV_ARGS(OUT, OS)                                                     \
+  (const T*)dout, (const T*)q, (const T*)k, (const T*)v, delta, lse, OUT,     \
+      nullptr, (int)Sq, (int)Sk, (int)N, (int)G, gs[0], gs[1], gs[2], qs[0],  \
+      qs[1], qs[2], ks[0], ks[1], ks[2], vs[0], vs[1], vs[2], ds[0], ds[1],   \
+      ls[0], ls[1], OS[0], OS[1], OS[2], scale, causal
+  if (G > 1)
+    bwd_dkv_kernel<T, D, 0, 64, 1>
+        <<<grid_kv, 512, 0, (hipStream_t)stream>>>(DKV_ARGS(dv, dvs));
+  else
+    bwd_dkv_kernel<T, D, 0, 64, 0>
+        <<<grid_kv, 512, 0, (hipStream_t)stream>>>(DKV_ARGS(dv, dvs));
   BA_CHECK_LAUNCH();
   if (plan == 2) {
     if (dkq_dbg == 1)
@@ -1095,21 +1151,23 @@ static int launch_bwd(const void* dout, const void* q, const void* k,
     bwd_dkq_kernel<T, D, 0><<<grid_dkq, 512, 0, (hipStream_t)stream>>>(DKQ_ARGS);
     BA_CHECK_LAUNCH();
   } else {
-    bwd_dkv_kernel<T, D, 1><<<grid_kv, 512, 0, (hipStream_t)stream>>>(
-        (const T*)dout, (const T*)q, (const T*)k, (const T*)v, delta, lse,
-        dk, nullptr, (int)Sq, (int)Sk, (int)N, gs[0], gs[1], gs[2], qs[0],
-        qs[1], qs[2], ks[0], ks[1], ks[2], vs[0], vs[1], vs[2], ds[0], ds[1],
-        ls[0], ls[1], dks[0], dks[1], dks[2], scale, causal);
+    if (G > 1)
+      bwd_dkv_kernel<T, D, 1, 64, 1>
+          <<<grid_kv, 512, 0, (hipStream_t)stream>>>(DKV_ARGS(dk, dks));
+    else
+      bwd_dkv_kernel<T, D, 1, 64, 0>
+          <<<grid_kv, 512, 0, (hipStream_t)stream>>>(DKV_ARGS(dk, dks));
     BA_CHECK_LAUNCH();
   }
+#undef DKV_ARGS
 #undef DKQ_ARGS
   return 0;
 }
 
-extern "C" int bahip_attn_bwd(
+extern "C" int bahip_attn_bwd_gqa(
     const void* dout, const void* q, const void* k, const void* v,
     const float* delta, const float* lse, float* dq, float* dk, float* dv,
-    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t D,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
     const int64_t do_strides[3], const int64_t q_strides[3],
     const int64_t k_strides[3], const int64_t v_strides[3],
     const int64_t delta_strides[2], const int64_t lse_strides[2],
@@ -1122,9 +1180,27 @@ extern "C" int bahip_attn_bwd(
                    (int)Sk);
   return ba_dispatch_td(D, dtype, [&](auto td) {
     return launch_bwd<typename decltype(td)::type, decltype(td)::D>(
-        dout, q, k, v, delta, lse, dq, dk, dv, B, Sq, Sk, N, do_strides,
+        dout, q, k, v, delta, lse, dq, dk, dv, B, Sq, Sk, N, Nk, do_strides,
         q_strides, k_strides, v_strides, delta_strides, lse_strides,
         dq_strides, dk_strides, dv_strides, softmax_scale, causal,
         deterministic, stream);
   });
+}
+
+// the equal-heads symbol: Nk = N
+extern "C" int bahip_attn_bwd(
+    const void* dout, const void* q, const void* k, const void* v,
+    const float* delta, const float* lse, float* dq, float* dk, float* dv,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t D,
+    const int64_t do_strides[3], const int64_t q_strides[3],
+    const int64_t k_strides[3], const int64_t v_strides[3],
+    const int64_t delta_strides[2], const int64_t lse_strides[2],
+    const int64_t dq_strides[3], const int64_t dk_strides[3],
+    const int64_t dv_strides[3], float softmax_scale, int causal,
+    int deterministic, int dtype, void* stream) {
+  return bahip_attn_bwd_gqa(dout, q, k, v, delta, lse, dq, dk, dv, B, Sq, Sk,
+                            N, N, D, do_strides, q_strides, k_strides,
+                            v_strides, delta_strides, lse_strides, dq_strides,
+                            dk_strides, dv_strides, softmax_scale, causal,
+                            deterministic, dtype, stream);
 }

@@ -24,6 +24,7 @@
 #include "attn_common.h"
 #include "attn_host.h"
 #include "fwd_variants.h"
+#include "gqa_heads.h"
 
 #include <stddef.h>
 
@@ -89,7 +90,7 @@ template <typename T, int D, int KVBLK, int OUT_STATE, int VPATH, int SUBT,
 __global__ __launch_bounds__(NT) void attn_fwd_kernel(
     const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
     float* __restrict__ o, float* __restrict__ lse,
-    int Sq, int Sk, int N,
+    int Sq, int Sk, int N, int G,
     int64_t q_sb, int64_t q_ss, int64_t q_sh,
     int64_t k_sb, int64_t k_ss, int64_t k_sh,
     int64_t v_sb, int64_t v_ss, int64_t v_sh,
@@ -131,8 +132,11 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
   const int q_row = qb + l31;
 
   const T* qp = q + (int64_t)b * q_sb + (int64_t)n * q_sh;
-  const T* kp = k + (int64_t)b * k_sb + (int64_t)n * k_sh;
-  const T* vp = v + (int64_t)b * v_sb + (int64_t)n * v_sh;
+  // grouped-query heads: q head n attends KV head n / G (wave-uniform,
+  // once per workgroup); q, o, lse and the carry-in state stay on n
+  const int nkv = n / G;
+  const T* kp = k + (int64_t)b * k_sb + (int64_t)nkv * k_sh;
+  const T* vp = v + (int64_t)b * v_sb + (int64_t)nkv * v_sh;
 
   // Q fragments: B-operand of S^T = mfma(K, Q); lane holds q row q_row,
   // elements d = 16*s + 8*hi + j  (8 contiguous -> one 16B load)
@@ -652,6 +656,22 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
       __syncthreads();
   };
   if constexpr (SUBT == 1) {
+    // Fix the steady loop's code placement.  The loop takes ~15 branches
+    // per tile and its rate depends on where their targets fall in the
+    // fetch lines: moving the identical loop by 12 bytes (27 prologue
+    // instructions for the n / G above) measured -3% on the headline
+    // forward, and padding it back restored the rate (DESIGN §11,
+    // profiles/gqa/).  The directive lands in the loop's preheader, so
+    // the loop's offset within a 128-byte line no longer follows the
+    // prologue's length.  Nothing in the language ties the statement to
+    // the loop header: the compiler is free to put preheader
+    // instructions after it, so this holds for the code a given
+    // compiler emits, and was checked in the disassembly of the default
+    // variant <0,1,512,2,0> (D=64/128, fp16/bf16, both OUT_STATE forms).
+    // For its D=128 carry-in form (the ring path) the result is the
+    // placement the tuned numbers were measured at.  The pad is a few
+    // s_nops executed once per workgroup.
+    asm volatile(".p2align 7");
     for (int tb = 0; tb < nt; tb += NBUF) {
       [[clang::always_inline]] tile_body(tb, ba_ic<0>{});
       if (tb + 1 < nt) [[clang::always_inline]] tile_body(tb + 1, ba_ic<1 % NBUF>{});
@@ -790,7 +810,7 @@ extern "C" const char* bahip_last_error(void) { return ba_g_err; }
 struct fwd_args {
   const void *q, *k, *v;
   float *o, *lse;
-  int Sq, Sk, N;
+  int Sq, Sk, N, G;
   int64_t q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh;
   float scale;
   int causal;
@@ -831,29 +851,37 @@ static void launch_fwd(const fwd_args& a, int64_t B, hipStream_t stream) {
   attn_fwd_kernel<T, D, 64, OUT_STATE, VPATH, SUBT, NT, NBUF, KREG>
       <<<fwd_grid(a, B, NT), dim3(NT), 0, stream>>>(
           (const T*)a.q, (const T*)a.k, (const T*)a.v, a.o, a.lse, a.Sq, a.Sk,
-          a.N, a.q_sb, a.q_ss, a.q_sh, a.k_sb, a.k_ss, a.k_sh, a.v_sb, a.v_ss,
+          a.N, a.G, a.q_sb, a.q_ss, a.q_sh, a.k_sb, a.k_ss, a.k_sh, a.v_sb, a.v_ss,
           a.v_sh, a.scale, a.causal, a.st_acc, a.st_m, a.st_l, a.a_sb, a.a_ss,
           a.a_sh, a.ml_sb, a.ml_sh, a.carry_in);
 }
 
-// Shared body of the three forward entry points.  out_state = 0: the
+// Shared body of every forward entry point (Nk = N for the equal-heads
+// symbols; the kernel gets the group size G = N / Nk).  out_state = 0: the
 // stateless tile (o, lse; state pointers null).  out_state = 1: the
 // carry-in accumulator (o/lse null), launched through hip_function when
 // one is given, else through the variant the BA_FWD_* knobs select.
 static int fwd_entry(void* hip_function, int out_state, const void* q,
                      const void* k, const void* v, float* o, float* lse,
-                     int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t D,
-                     const int64_t* qs, const int64_t* ks, const int64_t* vs,
-                     float scale, int causal, int dtype, float* acc, float* m,
+                     int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk,
+                     int64_t D, const int64_t* qs, const int64_t* ks,
+                     const int64_t* vs, float scale, int causal, int dtype,
+                     float* acc, float* m,
                      float* l, const int64_t* as, const int64_t* mls,
                      int carry_in, void* stream) {
   if (causal && Sq != Sk)
     return ba_fail(BAHIP_ERR_CAUSAL_SHAPE,
                    "causal tiles require Sq == Sk (%d vs %d)", (int)Sq,
                    (int)Sk);
+  const int64_t G = ba_gqa_group(N, Nk);
+  if (!G)
+    return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                   "q heads N=%d must be a positive multiple of kv heads "
+                   "Nk=%d",
+                   (int)N, (int)Nk);
   static const int64_t none[3] = {0, 0, 0};
   if (!out_state) as = mls = none;
-  const fwd_args a = {q, k, v, o, lse, (int)Sq, (int)Sk, (int)N,
+  const fwd_args a = {q, k, v, o, lse, (int)Sq, (int)Sk, (int)N, (int)G,
                       qs[0], qs[1], qs[2], ks[0], ks[1], ks[2],
                       vs[0], vs[1], vs[2], scale, causal, acc, m, l,
                       as[0], as[1], as[2], mls[0], mls[1], carry_in};
@@ -900,6 +928,31 @@ static int fwd_entry(void* hip_function, int out_state, const void* q,
   });
 }
 
+extern "C" int bahip_attn_fwd_gqa(
+    const void* q, const void* k, const void* v, float* o, float* lse,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    void* stream) {
+  return fwd_entry(nullptr, 0, q, k, v, o, lse, B, Sq, Sk, N, Nk, D, q_strides,
+                   k_strides, v_strides, softmax_scale, causal, dtype, nullptr,
+                   nullptr, nullptr, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int bahip_attn_fwd_accum_gqa(
+    void* hip_function, const void* q, const void* k, const void* v,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    float* acc, float* m, float* l, const int64_t acc_strides[3],
+    const int64_t ml_strides[2], int carry_in, void* stream) {
+  return fwd_entry(hip_function, 1, q, k, v, nullptr, nullptr, B, Sq, Sk, N,
+                   Nk, D, q_strides, k_strides, v_strides, softmax_scale,
+                   causal, dtype, acc, m, l, acc_strides, ml_strides, carry_in,
+                   stream);
+}
+
+// the equal-heads symbols: Nk = N
 extern "C" int bahip_attn_fwd(const void* q, const void* k, const void* v,
                               float* o, float* lse, int64_t B, int64_t Sq,
                               int64_t Sk, int64_t N, int64_t D,
@@ -907,9 +960,9 @@ extern "C" int bahip_attn_fwd(const void* q, const void* k, const void* v,
                               const int64_t k_strides[3],
                               const int64_t v_strides[3], float softmax_scale,
                               int causal, int dtype, void* stream) {
-  return fwd_entry(nullptr, 0, q, k, v, o, lse, B, Sq, Sk, N, D, q_strides,
-                   k_strides, v_strides, softmax_scale, causal, dtype, nullptr,
-                   nullptr, nullptr, nullptr, nullptr, 0, stream);
+  return bahip_attn_fwd_gqa(q, k, v, o, lse, B, Sq, Sk, N, N, D, q_strides,
+                            k_strides, v_strides, softmax_scale, causal, dtype,
+                            stream);
 }
 
 extern "C" int bahip_attn_fwd_accum(
@@ -919,10 +972,10 @@ extern "C" int bahip_attn_fwd_accum(
     float softmax_scale, int causal, int dtype, float* acc, float* m,
     float* l, const int64_t acc_strides[3], const int64_t ml_strides[2],
     int carry_in, void* stream) {
-  return bahip_attn_fwd_accum_fn(nullptr, q, k, v, B, Sq, Sk, N, D, q_strides,
-                                 k_strides, v_strides, softmax_scale, causal,
-                                 dtype, acc, m, l, acc_strides, ml_strides,
-                                 carry_in, stream);
+  return bahip_attn_fwd_accum_gqa(nullptr, q, k, v, B, Sq, Sk, N, N, D,
+                                  q_strides, k_strides, v_strides,
+                                  softmax_scale, causal, dtype, acc, m, l,
+                                  acc_strides, ml_strides, carry_in, stream);
 }
 
 extern "C" int bahip_attn_fwd_accum_fn(
@@ -932,10 +985,10 @@ extern "C" int bahip_attn_fwd_accum_fn(
     const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
     float* acc, float* m, float* l, const int64_t acc_strides[3],
     const int64_t ml_strides[2], int carry_in, void* stream) {
-  return fwd_entry(hip_function, 1, q, k, v, nullptr, nullptr, B, Sq, Sk, N, D,
-                   q_strides, k_strides, v_strides, softmax_scale, causal,
-                   dtype, acc, m, l, acc_strides, ml_strides, carry_in,
-                   stream);
+  return bahip_attn_fwd_accum_gqa(hip_function, q, k, v, B, Sq, Sk, N, N, D,
+                                  q_strides, k_strides, v_strides,
+                                  softmax_scale, causal, dtype, acc, m, l,
+                                  acc_strides, ml_strides, carry_in, stream);
 }
 
 extern "C" int bahip_attn_fwd_finalize(const float* acc, const float* m,

@@ -41,9 +41,10 @@ struct Strides3 {
   operator const int64_t*() const { return s; }
 };
 
-// per-tensor layout plus cross-tensor consistency vs q: batch/heads/head_dim
-// agree, k/v seqlens agree, dtypes are equal — a mismatch must raise here,
-// not read out of bounds on device.
+// per-tensor layout plus cross-tensor consistency vs q: batch/head_dim
+// agree, k/v heads and seqlens agree, q heads are a multiple of the k/v
+// heads (grouped-query: q head h attends kv head h / G), dtypes are equal
+// — a mismatch must raise here, not read out of bounds on device.
 void check_qkv3(const at::Tensor& q, const at::Tensor& k,
                 const at::Tensor& v) {
   check_qkv(q, "q");
@@ -51,8 +52,11 @@ void check_qkv3(const at::Tensor& q, const at::Tensor& k,
   check_qkv(v, "v");
   TORCH_CHECK(k.size(0) == q.size(0) && v.size(0) == q.size(0),
               "batch mismatch");
-  TORCH_CHECK(k.size(2) == q.size(2) && v.size(2) == q.size(2),
-              "heads mismatch");
+  TORCH_CHECK(v.size(2) == k.size(2), "k/v heads mismatch (", k.size(2),
+              " vs ", v.size(2), ")");
+  TORCH_CHECK(k.size(2) >= 1 && q.size(2) % k.size(2) == 0,
+              "heads mismatch: q heads N=", q.size(2),
+              " must be a multiple of kv heads Nk=", k.size(2));
   TORCH_CHECK(k.size(3) == q.size(3) && v.size(3) == q.size(3),
               "head_dim mismatch");
   TORCH_CHECK(v.size(1) == k.size(1), "k/v seqlen mismatch");
@@ -77,11 +81,11 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k,
   auto o = at::empty({B, Sq, N, D}, q.options().dtype(at::kFloat));
   auto lse = at::empty({B, N, Sq}, q.options().dtype(at::kFloat));
   auto stream = at::hip::getCurrentHIPStream().stream();
-  BA_CALL(bahip_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                         o.data_ptr<float>(), lse.data_ptr<float>(), B, Sq,
-                         Sk, N, D, Strides3(q), Strides3(k), Strides3(v),
-                         (float)softmax_scale, causal ? 1 : 0, dtype_code(q),
-                         stream));
+  BA_CALL(bahip_attn_fwd_gqa(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                             o.data_ptr<float>(), lse.data_ptr<float>(), B,
+                             Sq, Sk, N, k.size(2), D, Strides3(q), Strides3(k),
+                             Strides3(v), (float)softmax_scale, causal ? 1 : 0,
+                             dtype_code(q), stream));
   return {o, lse};
 }
 
@@ -105,9 +109,9 @@ void fwd_accum_call(void* asm_fn, const at::Tensor& q, const at::Tensor& k,
   TORCH_CHECK(l.stride(0) == mls[0] && l.stride(1) == mls[1],
               "m/l stride mismatch");
   auto stream = at::hip::getCurrentHIPStream().stream();
-  BA_CALL(bahip_attn_fwd_accum_fn(
-      asm_fn, q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Sq, Sk, N, D,
-      Strides3(q), Strides3(k), Strides3(v), (float)softmax_scale,
+  BA_CALL(bahip_attn_fwd_accum_gqa(
+      asm_fn, q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Sq, Sk, N,
+      k.size(2), D, Strides3(q), Strides3(k), Strides3(v), (float)softmax_scale,
       causal ? 1 : 0, dtype_code(q), acc.data_ptr<float>(),
       m.data_ptr<float>(), l.data_ptr<float>(), Strides3(acc), mls,
       carry_in ? 1 : 0, stream));
@@ -198,14 +202,13 @@ void attn_bwd_accum(const at::Tensor& dout, const at::Tensor& q,
   int64_t ds[2] = {delta.stride(0), delta.stride(1)};
   int64_t ls[2] = {lse.stride(0), lse.stride(1)};
   auto stream = at::hip::getCurrentHIPStream().stream();
-  BA_CALL(bahip_attn_bwd(dout.data_ptr(), q.data_ptr(), k.data_ptr(),
-                         v.data_ptr(), delta.data_ptr<float>(),
-                         lse.data_ptr<float>(), dq.data_ptr<float>(),
-                         dk.data_ptr<float>(), dv.data_ptr<float>(), B, Sq,
-                         Sk, N, D, Strides3(dout), Strides3(q), Strides3(k),
-                         Strides3(v), ds, ls, Strides3(dq), Strides3(dk),
-                         Strides3(dv), (float)softmax_scale, causal ? 1 : 0,
-                         deterministic ? 1 : 0, dtype_code(q), stream));
+  BA_CALL(bahip_attn_bwd_gqa(
+      dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+      delta.data_ptr<float>(), lse.data_ptr<float>(), dq.data_ptr<float>(),
+      dk.data_ptr<float>(), dv.data_ptr<float>(), B, Sq, Sk, N, k.size(2), D,
+      Strides3(dout), Strides3(q), Strides3(k), Strides3(v), ds, ls,
+      Strides3(dq), Strides3(dk), Strides3(dv), (float)softmax_scale,
+      causal ? 1 : 0, deterministic ? 1 : 0, dtype_code(q), stream));
 }
 
 std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
@@ -217,8 +220,10 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
   const auto Sk = k.size(1);
   // zero-filled: the kernels accumulate, so this equals fresh outputs
   auto dq = at::zeros({B, Sq, N, D}, q.options().dtype(at::kFloat));
-  auto dk = at::zeros({B, Sk, N, D}, q.options().dtype(at::kFloat));
-  auto dv = at::zeros({B, Sk, N, D}, q.options().dtype(at::kFloat));
+  // dk/dv take k/v's head count (Nk <= N with grouped-query heads)
+  const auto Nk = k.size(2);
+  auto dk = at::zeros({B, Sk, Nk, D}, q.options().dtype(at::kFloat));
+  auto dv = at::zeros({B, Sk, Nk, D}, q.options().dtype(at::kFloat));
   attn_bwd_accum(dout, q, k, v, delta, lse, softmax_scale, causal,
                  deterministic, dq, dk, dv);
   return {dq, dk, dv};

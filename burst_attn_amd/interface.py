@@ -21,6 +21,13 @@ MI355X-first redesign decisions (vs the reference):
     {delta-or-o, grad_output, q, lse} plus a separate travelling-dq ring
     with one extra final hop (``:291-396``).
 
+Grouped-query attention (GQA/MQA): ``k``/``v`` may carry fewer heads than
+``q`` — q ``[B, S, N, H]``, k/v ``[B, S, Nk, H]`` with ``N % Nk == 0``;
+query head h attends KV head ``h // (N // Nk)`` (the flash-attn
+convention).  K/V travel the ring UNEXPANDED (the forward payload and the
+comm buffers shrink N/Nk-fold), and ``k.grad``/``v.grad`` have Nk heads:
+the kernels sum each group's query heads in place.
+
 Causal load-balancing layouts (see oracle/partition.py):
   * ``OpBurstAttn``     — zigzag: rank r holds global chunks [r] and
     [2W-1-r]; per-round half-tile dispatch per ``:221-235`` (fwd) and
@@ -98,6 +105,33 @@ def _check_flash_arg(flash):
         )
 
 
+def _check_heads(q, k, v):
+    """q [B,S,N,H]; k/v [B,S,Nk,H] with N a multiple of Nk (N == Nk is
+    plain multi-head attention)."""
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError(
+            "q, k, v must be [B, S, heads, head_dim]; got shapes "
+            f"{tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}"
+        )
+    N, Nk, Nv = q.shape[2], k.shape[2], v.shape[2]
+    if Nk != Nv:
+        raise ValueError(
+            f"k and v head counts differ: k has Nk={Nk}, v has {Nv} "
+            f"(q has N={N})"
+        )
+    if Nk < 1 or N % Nk != 0:
+        raise ValueError(
+            f"q heads N={N} must be a multiple of kv heads Nk={Nk} "
+            "(grouped-query attention: query head h attends kv head "
+            "h // (N // Nk))"
+        )
+    if k.shape[3] != q.shape[3] or v.shape[3] != q.shape[3]:
+        raise ValueError(
+            f"head_dim differs: q {q.shape[3]}, k {k.shape[3]}, "
+            f"v {v.shape[3]} (N={N}, Nk={Nk})"
+        )
+
+
 def burst_attn_func(
     q: torch.Tensor,
     k: torch.Tensor,
@@ -110,6 +144,7 @@ def burst_attn_func(
     process_group=None,
     double_group=[None, None],
 ):
+    _check_heads(q, k, v)
     return OpBurstAttn.apply(
         q, k, v, softmax_scale, flash, causal, optimize_bwd_comm,
         deterministic, process_group, double_group,
@@ -128,6 +163,7 @@ def burst_attn_func_striped(
     process_group=None,
     double_group=[None, None],
 ):
+    _check_heads(q, k, v)
     return OpBurstAttnStrip.apply(
         q, k, v, softmax_scale, flash, causal, optimize_bwd_comm,
         deterministic, process_group, double_group,

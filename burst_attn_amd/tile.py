@@ -16,7 +16,8 @@ Provider contract (all tensors in flash layout [B, S, N, D]; lse/delta in
                                             (= rowsum(o*do); the flash bwd
                                             preprocess, cf. lao.py:247-269)
   bwd(do, q, k, v, delta, lse, scale,
-      causal, deterministic)             -> (dq, dk, dv fp32 [.,.,N,D])
+      causal, deterministic)             -> (dq fp32 [.,.,N,D],
+                                             dk, dv fp32 [.,.,Nk,D])
   bwd_accum(do, q, k, v, delta, lse,
       scale, causal, deterministic,
       dq, dk, dv)                        -> None; ADDS the tile's dq/dk/dv
@@ -29,6 +30,13 @@ Provider contract (all tensors in flash layout [B, S, N, D]; lse/delta in
   merge(o, lse, o_i, lse_i)              -> merged (o, lse); o [B,S,N,D]
                                             fp32, lse [B,S,N,1] fp32,
                                             per burst_utils.py:20-33.
+
+Head convention (grouped-query attention): q, do, o, dq and the fwd_accum
+state carry N heads; k, v, dk, dv carry Nk heads with N % Nk == 0.  Query
+head h attends KV head h // G, G = N // Nk (the flash-attn convention);
+dk/dv are the sum over the G query heads of each group; lse and delta
+stay per query head ([B, N, S]).  Nk == N is plain multi-head attention.
+No signature carries G: the shapes do.
 
 The default provider is the gfx950 HIP extension and FAILS LOUDLY if the
 extension is missing on a GPU machine — there is no CPU/eager fallback in

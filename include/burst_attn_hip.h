@@ -32,6 +32,17 @@
  *     style fused dK+dQ experiment with atomic fp32 dq, is not.
  *   - causal implies Sq == Sk (equal-length tiles; the ring's zigzag /
  *     striped bookkeeping reduces every other case to non-causal tiles).
+ *   - grouped-query heads (GQA/MQA): the *_gqa entry points take the KV
+ *     head count Nk after N.  q/do/dq are [B, S, N, D]; k/v and dk/dv are
+ *     [B, S, Nk, D] with N % Nk == 0 and G = N / Nk.  Query head h attends
+ *     KV head h / G (the flash-attn convention).  dk/dv receive the sum
+ *     over the G query heads of each group, accumulated inside one kernel
+ *     in a fixed order (bitwise deterministic).  lse, delta and the
+ *     carry-in state (acc, m, l) stay per query head.  The symbols without
+ *     the suffix are the Nk = N case.  Nk < 1 or N % Nk != 0 returns
+ *     BAHIP_ERR_UNSUPPORTED.  The BA_BWD_FUSED=1/2 and BA_BWD_DK_FLIP=1
+ *     experiment plans are equal-heads only and return
+ *     BAHIP_ERR_UNSUPPORTED when Nk != N.
  *   - stream is a hipStream_t.
  * Returns 0 on success; nonzero = error.  Every nonzero return sets the
  * calling thread's bahip_last_error() message and every success clears it.
@@ -49,7 +60,8 @@ extern "C" {
 #define BAHIP_BF16 1
 
 #define BAHIP_ERR_CAUSAL_SHAPE 1001   /* causal with Sq != Sk */
-#define BAHIP_ERR_UNSUPPORTED 1002    /* head_dim not 64/128, or dtype */
+#define BAHIP_ERR_UNSUPPORTED 1002    /* head_dim not 64/128, dtype, or
+                                         an invalid (N, Nk) head pair */
 #define BAHIP_ERR_DTYPE_MISMATCH 1003 /* o / dout dtypes differ */
 #define BAHIP_ERR_BAD_KNOB 1004       /* BA_FWD_* value outside its set */
 
@@ -59,6 +71,17 @@ int bahip_attn_fwd(
     const void* q, const void* k, const void* v,
     float* o, float* lse,
     int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t D,
+    const int64_t q_strides[3],
+    const int64_t k_strides[3],
+    const int64_t v_strides[3],
+    float softmax_scale, int causal, int dtype,
+    void* stream);
+
+/* bahip_attn_fwd with Nk KV heads (see "grouped-query heads" above) */
+int bahip_attn_fwd_gqa(
+    const void* q, const void* k, const void* v,
+    float* o, float* lse,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
     const int64_t q_strides[3],
     const int64_t k_strides[3],
     const int64_t v_strides[3],
@@ -92,6 +115,18 @@ int bahip_attn_fwd_accum_fn(
     float* acc, float* m, float* l, const int64_t acc_strides[3],
     const int64_t ml_strides[2], int carry_in, void* stream);
 
+/* bahip_attn_fwd_accum / bahip_attn_fwd_accum_fn with Nk KV heads:
+ * hip_function null launches the in-binary variant the BA_FWD_* knobs
+ * select, non-null the given module kernel. */
+int bahip_attn_fwd_accum_gqa(
+    void* hip_function,
+    const void* q, const void* k, const void* v,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    float* acc, float* m, float* l, const int64_t acc_strides[3],
+    const int64_t ml_strides[2], int carry_in, void* stream);
+
 /* o = acc / l cast to dtype; lse = ln(l) + m*ln2; contiguous full chunk */
 int bahip_attn_fwd_finalize(
     const float* acc, const float* m, const float* l, void* o, float* lse,
@@ -108,6 +143,20 @@ int bahip_attn_bwd(
     const float* delta, const float* lse,
     float* dq, float* dk, float* dv,
     int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t D,
+    const int64_t do_strides[3], const int64_t q_strides[3],
+    const int64_t k_strides[3], const int64_t v_strides[3],
+    const int64_t delta_strides[2], const int64_t lse_strides[2],
+    const int64_t dq_strides[3], const int64_t dk_strides[3],
+    const int64_t dv_strides[3],
+    float softmax_scale, int causal, int deterministic, int dtype,
+    void* stream);
+
+/* bahip_attn_bwd with Nk KV heads: dk/dv are [B, Sk, Nk, D] */
+int bahip_attn_bwd_gqa(
+    const void* dout, const void* q, const void* k, const void* v,
+    const float* delta, const float* lse,
+    float* dq, float* dk, float* dv,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
     const int64_t do_strides[3], const int64_t q_strides[3],
     const int64_t k_strides[3], const int64_t v_strides[3],
     const int64_t delta_strides[2], const int64_t lse_strides[2],
