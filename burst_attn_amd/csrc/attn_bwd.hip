@@ -11,7 +11,7 @@
 // in place (strided), which lets the ring layer accumulate across rounds
 // with no elementwise-add passes or per-round allocations.
 //
-// Kernel plans behind bahip_attn_bwd (selection: see launch_bwd; the
+// Kernel plans behind bahip_attn_bwd (selection: bwd_plans.h; the
 // `deterministic` argument does not choose between them):
 //   default "split8" (atomic-free, 8 tile GEMMs — flash-attn executes 5):
 //     1. bwd_preprocess: delta = rowsum(o * do) fp32  (flash's preprocess)
@@ -21,23 +21,15 @@
 //     3. dkdv kernels (kv-block resident, streams q/do):
 //          MODE 0 (dV): S = mfma(Q,K^T); dV^T += mfma(dO^T, P)
 //          MODE 1 (dK): + dP = mfma(dO,V^T); dK^T += mfma(Q^T, dS)
-//   BA_BWD_FUSED=2 "atomic6" (6 tile GEMMs — the flash-attn plan):
-//     1. bwd_preprocess
-//     2. bwd_dkq kernel (kv-resident, FLIPPED orientation: S^T = mfma(K,Q)
-//        with kv on the MFMA row axis and q on the lane axis, so lse/delta
-//        are lane-local — no per-row constant folding, no serial LDS->MFMA
-//        prologue):  S^T, dP^T, then
-//          dK^T += mfma(Q^T, dS)   (dS fragments via a per-wave LDS
-//                                   transpose of the dS^T D-layout)
-//          dQ   += mfma(dS^T, K^T) (fragments built in-register; partials
-//                                   LDS-reduced across waves, flushed with
-//                                   one global fp32 atomic-add per
-//                                   workgroup q-subtile)
-//     3. dkdv MODE 0 (dV) as above.
+//   BA_BWD_FUSED=1 "dkvf7" (7 GEMMs, atomic-free): dq kernel + the fused
+//     flipped dK+dV kernel (bwd_dkq_kernel FUSE_DV=1, described above it)
+//   BA_BWD_FUSED=2 "atomic6" (6 GEMMs — the flash-attn plan): the fused
+//     dK+dQ kernel (bwd_dkq_kernel FUSE_DQ=1, fp32 atomic dq) + dkdv MODE 0
 // Operand scheme and LDS swizzle: see attn_common.h.
 
 #include "attn_common.h"
 #include "attn_host.h"
+#include "bwd_plans.h"
 #include "gqa_heads.h"
 
 namespace {
@@ -293,8 +285,7 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
 // (~90 VGPRs) at the 2-waves/SIMD budget; split, each kernel is register
 // -clean and runs at the dq kernel's rate.  Cost: S is recomputed (the
 // backward executes 8 tile GEMMs total vs flash-attn's 5).
-// MODE: 0 = dV (dv^T += mfma(dO^T, P)); 1 = dK (dk^T += mfma(Q^T, dS));
-//       2 = fused dK+dV (both accumulators; 8-wave; may spill — A/B)
+// MODE: 0 = dV (dv^T += mfma(dO^T, P)); 1 = dK (dk^T += mfma(Q^T, dS)).
 // QBLK: streamed q-tile rows (128 for dV measured -8%: 27-VGPR spills).
 // GQA: 0 = one q head per workgroup (blockIdx.y = q head = kv head; G is
 //   ignored) — the equal-heads kernel, unchanged.
@@ -313,8 +304,7 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
     const T* __restrict__ dout, const T* __restrict__ q,
     const T* __restrict__ k, const T* __restrict__ v,
     const float* __restrict__ delta, const float* __restrict__ lse,
-    float* __restrict__ dout_acc, float* __restrict__ dout_acc2,
-    int Sq, int Sk, int N, int G,
+    float* __restrict__ dout_acc, int Sq, int Sk, int N, int G,
     int64_t g_sb, int64_t g_ss, int64_t g_sh,
     int64_t q_sb, int64_t q_ss, int64_t q_sh,
     int64_t k_sb, int64_t k_ss, int64_t k_sh,
@@ -329,8 +319,8 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
   constexpr int NT = 512;
   constexpr int PT = (QBLK * D / 8) / NT;
   // images per buffer: MODE_DV: [Q row-major | dO^T]; MODE_DK:
-  // [Q row-major | dO row-major | Q^T]; MODE 2: all four
-  constexpr int IMGS = MODE == 0 ? 2 : (MODE == 1 ? 3 : 4);
+  // [Q row-major | dO row-major | Q^T]
+  constexpr int IMGS = MODE == 0 ? 2 : 3;
 
   // one LDS object (a second __shared__ forces vmcnt(0) on every ds_read
   // — cdna guide §5 trap 4a).  lse/delta do NOT go through LDS: a
@@ -347,9 +337,6 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
   };
   auto ldsQT = [&](int buf) -> T* {
     return lds + buf * (IMGS * QBLK * D) + 2 * QBLK * D;
-  };
-  auto ldsGT2 = [&](int buf) -> T* {  // MODE 2 only: dO^T as 4th image
-    return lds + buf * (IMGS * QBLK * D) + 3 * QBLK * D;
   };
 
   const int tid = threadIdx.x;
@@ -370,7 +357,7 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
   const float* lp_ = lse + b * l_sb + n0 * l_sh;
 
   // resident K (always, for S); resident V when dP is needed
-  frag kf[D / 16], vf[MODE >= 1 ? D / 16 : 1];
+  frag kf[D / 16], vf[MODE == 1 ? D / 16 : 1];
   {
     const T* kp = k + b * k_sb + (int64_t)n * k_sh;
     const T* vp = v + b * v_sb + (int64_t)n * v_sh;
@@ -380,26 +367,22 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
         kf[s] = __builtin_bit_cast(
             frag,
             *(const u32x4_t*)(kp + (int64_t)kv_col * k_ss + 16 * s + 8 * hi));
-        if (MODE >= 1)
+        if (MODE == 1)
           vf[s] = __builtin_bit_cast(
               frag,
               *(const u32x4_t*)(vp + (int64_t)kv_col * v_ss + 16 * s + 8 * hi));
       } else {
         u32x4_t z = {0, 0, 0, 0};
         kf[s] = __builtin_bit_cast(frag, z);
-        if (MODE >= 1) vf[s] = __builtin_bit_cast(frag, z);
+        if (MODE == 1) vf[s] = __builtin_bit_cast(frag, z);
       }
     }
   }
   const float c2 = scale * BA_LOG2E;
 
   f32x16_t acc[D / 32];
-  f32x16_t acc2[MODE == 2 ? D / 32 : 1];  // MODE 2: dV accumulator
 #pragma unroll
   for (int dt = 0; dt < D / 32; ++dt) acc[dt] = (f32x16_t)(0.f);
-  if (MODE == 2)
-#pragma unroll
-    for (int dt = 0; dt < D / 32; ++dt) acc2[dt] = (f32x16_t)(0.f);
 
   // causal: q tiles wholly before this workgroup's kv rows are masked
   const int t0 = causal ? (blockIdx.x * 256) / QBLK : 0;
@@ -432,7 +415,7 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
       const int qc = qg < Sq ? qg : (Sq - 1);
       // clamped rows contaminate nothing: the q_g < Sq mask zeroes p/dS
       l2[qs].x = lpg[qc] * BA_LOG2E;
-      l2[qs].y = (MODE >= 1) ? dpg[qc] : 0.f;
+      l2[qs].y = (MODE == 1) ? dpg[qc] : 0.f;
     }
   };
   auto write_lds = [&](int buf, const u32x4_t* qreg, const u32x4_t* greg) {
@@ -449,8 +432,6 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
         // address set spills ~47 VGPRs here (measured -14% fwd+bwd)
         *(u32x4_t*)((char*)ldsG(buf) + byte) = greg[c];
         ba_st_transposed<T, QBLK, SWZ_T, 7>(ldsQT(buf), row, col8 * 8, qreg[c]);
-        if (MODE == 2)
-          ba_st_tr16row<T, D>(ldsGT2(buf), row, col8 * 8, greg[c]);
       }
     }
   };
@@ -515,13 +496,13 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
         }
         f32x16_t st = MT::mma(a_lse, ones01, (f32x16_t)(0.f));
         f32x16_t dpt = (f32x16_t)(0.f);
-        if (MODE >= 1) dpt = MT::mma(a_dlt, ones0, dpt);
+        if (MODE == 1) dpt = MT::mma(a_dlt, ones0, dpt);
 #pragma unroll
         for (int s = 0; s < D / 16; ++s) {
           frag qfr = ba_ld_rowslice<T, D, SWZ>(ldsQ(cur), qs * 32 + l31,
                                                16 * s + 8 * hi);
           st = MT::mma(qfr, kf[s], st);
-          if (MODE >= 1) {
+          if (MODE == 1) {
             frag gfr = ba_ld_rowslice<T, D, SWZ>(ldsG(cur), qs * 32 + l31,
                                                  16 * s + 8 * hi);
             dpt = MT::mma(gfr, vf[s], dpt);
@@ -535,19 +516,11 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
               q_g < Sq && kv_col < Sk && (!causal || q_g >= kv_col);
           const float e = valid ? st[r] * c2 : BA_NEG_BIG;
           const float p = ba_exp2(e);
-          if (MODE == 0) {
-            st[r] = p;  // P for dV
-          } else if (MODE == 1) {
-            st[r] = p * dpt[r] * scale;  // dS for dK
-          } else {
-            dpt[r] = p * dpt[r] * scale;  // dS
-            st[r] = p;                    // P
-          }
+          // MODE_DV: P; MODE_DK: dS
+          st[r] = (MODE == 0) ? p : p * dpt[r] * scale;
         }
         frag f01[2];
         ba_build_frag_pair<T>(st, f01);
-        frag f01b[MODE == 2 ? 2 : 1];
-        if (MODE == 2) ba_build_frag_pair<T>(dpt, (frag*)f01b);
 #pragma unroll
         for (int dt = 0; dt < D / 32; ++dt) {
           const int drow = dt * 32 + l31;
@@ -557,15 +530,7 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
             const T* timg = (MODE == 0) ? ldsG(cur) : ldsQT(cur);
             frag tf = ba_ld_rowslice<T, QBLK, SWZ_T, 7>(
                 timg, drow, qs * 32 + 16 * u + 8 * hi);
-            if (MODE == 2) {
-              // acc = dK (dS frags), acc2 = dV (P frags via dO^T)
-              acc[dt] = MT::mma(tf, f01b[u], acc[dt]);
-              frag gtf = ba_ld_tr16_frag<T, D>(ldsGT2(cur), lane,
-                                               qs * 32 + 16 * u, dt * 32);
-              acc2[dt] = MT::mma(gtf, f01[u], acc2[dt]);
-            } else {
-              acc[dt] = MT::mma(tf, f01[u], acc[dt]);
-            }
+            acc[dt] = MT::mma(tf, f01[u], acc[dt]);
           }
         }
       }
@@ -585,14 +550,6 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         row[dt * 32 + ba_crow(r, hi)] += acc[dt][r];
-    if (MODE == 2) {
-      float* row2 = dout_acc2 + b * o_sb + (int64_t)kv_col * o_ss + n * o_sh;
-#pragma unroll
-      for (int dt = 0; dt < D / 32; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          row2[dt * 32 + ba_crow(r, hi)] += acc2[dt][r];
-    }
   }
 }
 
@@ -1038,152 +995,157 @@ extern "C" int bahip_attn_bwd_preprocess(
   });
 }
 
-// plan selection (all plans accumulate into dq/dk/dv; plans 0 and 1 are
-// bitwise deterministic — the `deterministic` flag is honoured by
-// construction):
-//   plan 0 "split8" (DEFAULT): dq kernel + split dV (MODE 0) + split dK
-//     (MODE 1) — 8 tile GEMMs, two-pass dq, atomic-free.  Fastest
-//     measured plan on gfx950 (tools/dkq_probe.hip round 2).
-//     BA_BWD_DK_FLIP=1 swaps MODE 1 for the flipped FUSE_DQ=0 kernel
-//     (measured equal, 142 vs 137 ms at s=65536).
-//   plan 1 "dkvf7" (BA_BWD_FUSED=1): dq kernel + fused flipped dK+dV —
-//     7 tile GEMMs, atomic-free, but the QBLK=32 single-workgroup
-//     structure + P/dS scratch round trips measured SLOWER than split8
-//     (260 vs 230 ms for the dK+dV part at s=65536); kept as the
-//     documented experiment.
-//   plan 2 "atomic6" (BA_BWD_FUSED=2): flash-attn's plan — fused dK+dQ
-//     with fp32 atomic dq + split dV.  6 GEMMs but MEASURED DEAD on
-//     gfx950 (tools/dkq_probe.hip: LDS ds_add ~2.6 s, global fp32
-//     atomics ~1.8 s at this density — atomics drop their L2 line);
-//     kept for the record and for re-testing on future silicon.
-template <typename T, int D>
-static int launch_bwd(const void* dout, const void* q, const void* k,
-                      const void* v, const float* delta, const float* lse,
-                      float* dq, float* dk, float* dv, int64_t B, int64_t Sq,
-                      int64_t Sk, int64_t N, int64_t Nk, const int64_t* gs,
-                      const int64_t* qs, const int64_t* ks, const int64_t* vs,
-                      const int64_t* ds, const int64_t* ls,
-                      const int64_t* dqs, const int64_t* dks,
-                      const int64_t* dvs, float scale, int causal,
-                      int deterministic, void* stream) {
-  // read per call (cheap at one bwd invocation) so tests can flip plans
-  const int env_fused = ba_env_int("BA_BWD_FUSED", -1);
-  const int dk_flip = ba_env_int("BA_BWD_DK_FLIP", 0);
-  const int dkq_dbg = ba_env_int("BA_DKQ_DBG", 0);
-  (void)deterministic;  // plans 0/1 are deterministic by construction
-  const int plan = env_fused >= 0 ? env_fused : 0;
-  const int64_t G = ba_gqa_group(N, Nk);
-  if (!G)
-    return ba_fail(BAHIP_ERR_UNSUPPORTED,
-                   "q heads N=%d must be a positive multiple of kv heads "
-                   "Nk=%d",
-                   (int)N, (int)Nk);
-  // the bwd_dkq_kernel experiment plans are equal-heads only
-  if (G > 1 && (plan == 1 || plan == 2))
-    return ba_fail(BAHIP_ERR_UNSUPPORTED,
-                   "BA_BWD_FUSED=%d does not support grouped-query heads "
-                   "(N=%d, Nk=%d)",
-                   plan, (int)N, (int)Nk);
-  if (G > 1 && dk_flip)
-    return ba_fail(BAHIP_ERR_UNSUPPORTED,
-                   "BA_BWD_DK_FLIP=%d does not support grouped-query heads "
-                   "(N=%d, Nk=%d)",
-                   dk_flip, (int)N, (int)Nk);
-  // kv-resident kernels: one workgroup column per KV head
-  dim3 grid_kv((unsigned)((Sk + 255) / 256), (unsigned)Nk, (unsigned)B);
-  // head-first grid for the dkq/dkvf kernels
-  dim3 grid_dkq((unsigned)N, (unsigned)((Sk + 255) / 256), (unsigned)B);
-  dim3 grid_dq((unsigned)((Sq + 255) / 256), (unsigned)N, (unsigned)B);
+// ---- backward launch layer --------------------------------------------
+// Which kernels a knob combination launches: ba_bwd_select, bwd_plans.h;
+// what was measured for each plan: DESIGN.md.  All plans accumulate into
+// dq/dk/dv; split8 and dkvf7 are bitwise deterministic (the
+// `deterministic` flag is honoured by construction).
+//
+// One field per kernel parameter, in kernel order; the launch templates
+// expand a struct into the <<<>>> call and derive the grid, and
+// tools/dkq_probe.hip launches through the same pairs.  bwd_dq_kernel and
+// bwd_dkv_kernel take the same list — the inputs, one fp32 accumulator
+// (dq; dv for MODE 0, dk for MODE 1) and its strides — so they share one.
+struct bwd_dq_args {
+  const void *dout, *q, *k, *v;
+  const float *delta, *lse;
+  float* out;
+  int Sq, Sk, N, G;
+  int64_t g_sb, g_ss, g_sh, q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss,
+      v_sh, d_sb, d_sh, l_sb, l_sh, o_sb, o_ss, o_sh;
+  float scale;
+  int causal;
+};
+using bwd_dkv_args = bwd_dq_args;
+using bwd_dq_kernel_t = decltype(&bwd_dq_kernel<_Float16, 128, 0>);
+static_assert(
+    std::is_same_v<bwd_dq_kernel_t,
+                   decltype(&bwd_dkv_kernel<_Float16, 128, 0, 64, 0>)> &&
+        sizeof(bwd_dq_args) == kernarg_size<bwd_dq_kernel_t>::value,
+    "bwd_dq_args must mirror bwd_dq_kernel's and bwd_dkv_kernel's parameters");
 
-#define DKQ_ARGS                                                              \
-  (const T*)dout, (const T*)q, (const T*)k, (const T*)v, delta, lse, dq, dk, \
-      dv, (int)Sq, (int)Sk, (int)N, gs[0], gs[1], gs[2], qs[0], qs[1],        \
-      qs[2], ks[0], ks[1], ks[2], vs[0], vs[1], vs[2], ds[0], ds[1], ls[0],   \
-      ls[1], dqs[0], dqs[1], dqs[2], dks[0], dks[1], dks[2], dvs[0], dvs[1],  \
-      dvs[2], scale, causal
+template <typename T, typename K>
+static void launch_acc(K kernel, dim3 grid, const bwd_dq_args& a,
+                       hipStream_t stream) {
+  kernel<<<grid, 512, 0, stream>>>(
+      (const T*)a.dout, (const T*)a.q, (const T*)a.k, (const T*)a.v, a.delta,
+      a.lse, a.out, a.Sq, a.Sk, a.N, a.G, a.g_sb, a.g_ss, a.g_sh, a.q_sb,
+      a.q_ss, a.q_sh, a.k_sb, a.k_ss, a.k_sh, a.v_sb, a.v_ss, a.v_sh, a.d_sb,
+      a.d_sh, a.l_sb, a.l_sh, a.o_sb, a.o_ss, a.o_sh, a.scale, a.causal);
+}
 
-  const int dqp = ba_env_int("BA_DQ_PIPE", 0);
-  if (plan != 2) {
-#define DQ_ARGS                                                               \
-  (const T*)dout, (const T*)q, (const T*)k, (const T*)v, delta, lse, dq,      \
-      (int)Sq, (int)Sk, (int)N, (int)G, gs[0], gs[1], gs[2], qs[0], qs[1],    \
-      qs[2], ks[0], ks[1], ks[2], vs[0], vs[1], vs[2], ds[0], ds[1], ls[0],   \
-      ls[1], dqs[0], dqs[1], dqs[2], scale, causal
-    if (dqp)
-      bwd_dq_kernel<T, D, 1><<<grid_dq, 512, 0, (hipStream_t)stream>>>(DQ_ARGS);
-    else
-      bwd_dq_kernel<T, D, 0><<<grid_dq, 512, 0, (hipStream_t)stream>>>(DQ_ARGS);
-#undef DQ_ARGS
-    BA_CHECK_LAUNCH();
-  }
-  if (plan == 1) {
-    bwd_dkq_kernel<T, D, 0, 0, 32, 1>
-        <<<grid_dkq, 512, 0, (hipStream_t)stream>>>(DKQ_ARGS);
-    BA_CHECK_LAUNCH();
-    return 0;
-  }
-  // G = 1 runs the equal-heads instantiation (GQA = 0), G > 1 the
-  // group-loop one; OUT/OS = the accumulator and its strides
-#define DKV_ARGS(OUT, OS)                                                     \
-  (const T*)dout, (const T*)q, (const T*)k, (const T*)v, delta, lse, OUT,     \
-      nullptr, (int)Sq, (int)Sk, (int)N, (int)G, gs[0], gs[1], gs[2], qs[0],  \
-      qs[1], qs[2], ks[0], ks[1], ks[2], vs[0], vs[1], vs[2], ds[0], ds[1],   \
-      ls[0], ls[1], OS[0], OS[1], OS[2], scale, causal
-  if (G > 1)
-    bwd_dkv_kernel<T, D, 0, 64, 1>
-        <<<grid_kv, 512, 0, (hipStream_t)stream>>>(DKV_ARGS(dv, dvs));
-  else
-    bwd_dkv_kernel<T, D, 0, 64, 0>
-        <<<grid_kv, 512, 0, (hipStream_t)stream>>>(DKV_ARGS(dv, dvs));
-  BA_CHECK_LAUNCH();
-  if (plan == 2) {
-    if (dkq_dbg == 1)
-      bwd_dkq_kernel<T, D, 1, 1>
-          <<<grid_dkq, 512, 0, (hipStream_t)stream>>>(DKQ_ARGS);
-    else if (dkq_dbg == 2)
-      bwd_dkq_kernel<T, D, 1, 2>
-          <<<grid_dkq, 512, 0, (hipStream_t)stream>>>(DKQ_ARGS);
-    else
-      bwd_dkq_kernel<T, D, 1, 0>
-          <<<grid_dkq, 512, 0, (hipStream_t)stream>>>(DKQ_ARGS);
-    BA_CHECK_LAUNCH();
-  } else if (dk_flip) {
-    bwd_dkq_kernel<T, D, 0><<<grid_dkq, 512, 0, (hipStream_t)stream>>>(DKQ_ARGS);
-    BA_CHECK_LAUNCH();
-  } else {
-    if (G > 1)
-      bwd_dkv_kernel<T, D, 1, 64, 1>
-          <<<grid_kv, 512, 0, (hipStream_t)stream>>>(DKV_ARGS(dk, dks));
-    else
-      bwd_dkv_kernel<T, D, 1, 64, 0>
-          <<<grid_kv, 512, 0, (hipStream_t)stream>>>(DKV_ARGS(dk, dks));
-    BA_CHECK_LAUNCH();
-  }
-#undef DKV_ARGS
-#undef DKQ_ARGS
-  return 0;
+template <typename T, int D, int DQP>
+static void launch_dq(const bwd_dq_args& a, int64_t B, hipStream_t stream) {
+  const dim3 grid((unsigned)((a.Sq + 255) / 256), (unsigned)a.N, (unsigned)B);
+  launch_acc<T>(bwd_dq_kernel<T, D, DQP>, grid, a, stream);
+}
+
+// one workgroup column per KV head; G > 1 runs the group-loop (GQA = 1) form
+template <typename T, int D, int MODE>
+static void launch_dkv(const bwd_dkv_args& a, int64_t B, hipStream_t stream) {
+  const dim3 grid((unsigned)((a.Sk + 255) / 256), (unsigned)(a.N / a.G),
+                  (unsigned)B);
+  launch_acc<T>(a.G > 1 ? bwd_dkv_kernel<T, D, MODE, 64, 1>
+                        : bwd_dkv_kernel<T, D, MODE, 64, 0>,
+                grid, a, stream);
+}
+
+struct bwd_dkq_args {
+  const void *dout, *q, *k, *v;
+  const float *delta, *lse;
+  float *dq, *dk, *dv;
+  int Sq, Sk, N;
+  int64_t g_sb, g_ss, g_sh, q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss,
+      v_sh, d_sb, d_sh, l_sb, l_sh, dq_sb, dq_ss, dq_sh, dk_sb, dk_ss, dk_sh,
+      dv_sb, dv_ss, dv_sh;
+  float scale;
+  int causal;
+};
+static_assert(sizeof(bwd_dkq_args) ==
+                  kernarg_size<decltype(&bwd_dkq_kernel<_Float16, 128, 0>)>::value,
+              "bwd_dkq_args must mirror bwd_dkq_kernel's parameter list");
+
+// head-first grid (see the atomic-contention note above bwd_dkq_kernel)
+template <typename T, int D, int FUSE_DQ, int DBG = 0, int SCRW = 64,
+          int FUSE_DV = 0>
+static void launch_dkq(const bwd_dkq_args& a, int64_t B, hipStream_t stream) {
+  const dim3 grid((unsigned)a.N, (unsigned)((a.Sk + 255) / 256), (unsigned)B);
+  bwd_dkq_kernel<T, D, FUSE_DQ, DBG, SCRW, FUSE_DV><<<grid, 512, 0, stream>>>(
+      (const T*)a.dout, (const T*)a.q, (const T*)a.k, (const T*)a.v, a.delta,
+      a.lse, a.dq, a.dk, a.dv, a.Sq, a.Sk, a.N, a.g_sb, a.g_ss, a.g_sh, a.q_sb,
+      a.q_ss, a.q_sh, a.k_sb, a.k_ss, a.k_sh, a.v_sb, a.v_ss, a.v_sh, a.d_sb,
+      a.d_sh, a.l_sb, a.l_sh, a.dq_sb, a.dq_ss, a.dq_sh, a.dk_sb, a.dk_ss,
+      a.dk_sh, a.dv_sb, a.dv_ss, a.dv_sh, a.scale, a.causal);
 }
 
 extern "C" int bahip_attn_bwd_gqa(
     const void* dout, const void* q, const void* k, const void* v,
     const float* delta, const float* lse, float* dq, float* dk, float* dv,
     int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
-    const int64_t do_strides[3], const int64_t q_strides[3],
-    const int64_t k_strides[3], const int64_t v_strides[3],
-    const int64_t delta_strides[2], const int64_t lse_strides[2],
-    const int64_t dq_strides[3], const int64_t dk_strides[3],
-    const int64_t dv_strides[3], float softmax_scale, int causal,
-    int deterministic, int dtype, void* stream) {
+    const int64_t gs[3], const int64_t qs[3], const int64_t ks[3],
+    const int64_t vs[3], const int64_t ds[2], const int64_t ls[2],
+    const int64_t dqs[3], const int64_t dks[3], const int64_t dvs[3],
+    float scale, int causal, int deterministic, int dtype, void* stream) {
+  (void)deterministic;  // only atomic6 is not deterministic by construction
   if (causal && Sq != Sk)
     return ba_fail(BAHIP_ERR_CAUSAL_SHAPE,
                    "causal tiles require Sq == Sk (%d vs %d)", (int)Sq,
                    (int)Sk);
+  const int G = (int)ba_gqa_group(N, Nk);
+  if (!G)
+    return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                   "q heads N=%d must be a positive multiple of kv heads "
+                   "Nk=%d",
+                   (int)N, (int)Nk);
+  // read per call (cheap at one bwd invocation) so tests can flip plans
+  ba_bwd_knobs kn;
+  kn.fused = ba_env_int(BA_BWD_KNOB_SPECS[0].env, kn.fused);
+  kn.dk_flip = ba_env_int(BA_BWD_KNOB_SPECS[1].env, kn.dk_flip);
+  kn.dq_pipe = ba_env_int(BA_BWD_KNOB_SPECS[2].env, kn.dq_pipe);
+  kn.dkq_dbg = ba_env_int(BA_BWD_KNOB_SPECS[3].env, kn.dkq_dbg);
+  const ba_bwd_plan plan = ba_bwd_select(kn, G);
+  if (plan.verdict == BA_BWD_BAD_VALUE)
+    return ba_fail(BAHIP_ERR_BAD_KNOB, "%s=%d is not an accepted value",
+                   plan.knob, plan.value);
+  if (plan.verdict == BA_BWD_NO_GQA)
+    return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                   "%s=%d does not support grouped-query heads "
+                   "(N=%d, Nk=%d)",
+                   plan.knob, plan.value, (int)N, (int)Nk);
+  const int iSq = (int)Sq, iSk = (int)Sk, iN = (int)N;
+  const auto acc_into = [&](float* out, const int64_t* os) -> bwd_dq_args {
+    return {dout, q, k, v, delta, lse, out, iSq, iSk, iN, G,
+            gs[0], gs[1], gs[2], qs[0], qs[1], qs[2], ks[0], ks[1], ks[2],
+            vs[0], vs[1], vs[2], ds[0], ds[1], ls[0], ls[1],
+            os[0], os[1], os[2], scale, causal};
+  };
+  const bwd_dq_args dqa = acc_into(dq, dqs);
+  const bwd_dkv_args dva = acc_into(dv, dvs), dka = acc_into(dk, dks);
+  const bwd_dkq_args dkqa = {
+      dout, q, k, v, delta, lse, dq, dk, dv, iSq, iSk, iN,
+      gs[0], gs[1], gs[2], qs[0], qs[1], qs[2], ks[0], ks[1], ks[2],
+      vs[0], vs[1], vs[2], ds[0], ds[1], ls[0], ls[1],
+      dqs[0], dqs[1], dqs[2], dks[0], dks[1], dks[2],
+      dvs[0], dvs[1], dvs[2], scale, causal};
   return ba_dispatch_td(D, dtype, [&](auto td) {
-    return launch_bwd<typename decltype(td)::type, decltype(td)::D>(
-        dout, q, k, v, delta, lse, dq, dk, dv, B, Sq, Sk, N, Nk, do_strides,
-        q_strides, k_strides, v_strides, delta_strides, lse_strides,
-        dq_strides, dk_strides, dv_strides, softmax_scale, causal,
-        deterministic, stream);
+    using T = typename decltype(td)::type;
+    constexpr int TD = decltype(td)::D;
+    const hipStream_t st = (hipStream_t)stream;
+    for (int i = 0; i < plan.n_steps; ++i) {
+      switch (plan.steps[i]) {
+        case BA_STEP_DQ: launch_dq<T, TD, 0>(dqa, B, st); break;
+        case BA_STEP_DQ_PIPE: launch_dq<T, TD, 1>(dqa, B, st); break;
+        case BA_STEP_DV: launch_dkv<T, TD, 0>(dva, B, st); break;
+        case BA_STEP_DK: launch_dkv<T, TD, 1>(dka, B, st); break;
+        case BA_STEP_DK_FLIPPED: launch_dkq<T, TD, 0>(dkqa, B, st); break;
+        case BA_STEP_DKDV_FUSED: launch_dkq<T, TD, 0, 0, 32, 1>(dkqa, B, st); break;
+        case BA_STEP_DKDQ_ATOMIC: launch_dkq<T, TD, 1, 0>(dkqa, B, st); break;
+        case BA_STEP_DKDQ_DBG1: launch_dkq<T, TD, 1, 1>(dkqa, B, st); break;
+        case BA_STEP_DKDQ_DBG2: launch_dkq<T, TD, 1, 2>(dkqa, B, st); break;
+      }
+      BA_CHECK_LAUNCH();
+    }
+    return 0;
   });
 }
 

@@ -30,7 +30,6 @@
 
 namespace {
 
-
 // OUT_STATE=0: write normalised o (fp32) + lse — the stateless tile.
 // OUT_STATE=1: carry-in/carry-out accumulator state (acc = unnormalised
 // O, m = running max in the exp2 domain, l = running sum) — the fused
@@ -774,7 +773,6 @@ __global__ void mfma_probe_kernel(const T* a, const T* b, float* d) {
   for (int r = 0; r < 16; ++r) d[ba_crow(r, hi) * 32 + l31] = c[r];
 }
 
-
 // ---- ds_read_tr16_b64 semantics probe (test/dev support).
 // Fills LDS with element-index pattern, issues the transpose-read with a
 // per-mode address pattern, dumps each lane's 4 returned u16s.
@@ -819,17 +817,6 @@ struct fwd_args {
   int carry_in;
 };
 
-// explicit-kernarg segment size of a kernel, from its parameter types
-template <typename F>
-struct kernarg_size;
-template <typename... P>
-struct kernarg_size<void (*)(P...)> {
-  static constexpr size_t value = [] {
-    size_t off = 0;
-    ((off = (off + alignof(P) - 1) / alignof(P) * alignof(P) + sizeof(P)), ...);
-    return off;
-  }();
-};
 using production_kernel_t = decltype(&attn_fwd_kernel<
     _Float16, 128, 64, 1, BA_FWD_PRODUCTION.vpath, BA_FWD_PRODUCTION.subt,
     BA_FWD_PRODUCTION.nt, BA_FWD_PRODUCTION.nbuf, BA_FWD_PRODUCTION.kreg>);

@@ -48,6 +48,18 @@ inline int ba_launch_status() {
     if (int rc_ = ba_launch_status()) return rc_;  \
   } while (0)
 
+// explicit-kernarg segment size of a kernel, from its parameter types
+template <typename F>
+struct kernarg_size;
+template <typename... P>
+struct kernarg_size<void (*)(P...)> {
+  static constexpr size_t value = [] {
+    size_t off = 0;
+    ((off = (off + alignof(P) - 1) / alignof(P) * alignof(P) + sizeof(P)), ...);
+    return off;
+  }();
+};
+
 // f(ba_td<T, D>{}) for the supported (head_dim, dtype) pairs, else 1002.
 template <typename T, int D_>
 struct ba_td {

@@ -63,7 +63,9 @@ extern "C" {
 #define BAHIP_ERR_UNSUPPORTED 1002    /* head_dim not 64/128, dtype, or
                                          an invalid (N, Nk) head pair */
 #define BAHIP_ERR_DTYPE_MISMATCH 1003 /* o / dout dtypes differ */
-#define BAHIP_ERR_BAD_KNOB 1004       /* BA_FWD_* value outside its set */
+#define BAHIP_ERR_BAD_KNOB 1004       /* a BA_FWD_* knob, BA_BWD_FUSED,
+                                         BA_BWD_DK_FLIP, BA_DQ_PIPE or
+                                         BA_DKQ_DBG outside its set */
 
 const char* bahip_last_error(void);
 

@@ -345,6 +345,76 @@ def test_bwd_alt_plans_vs_split(s, plan, causal, dtype, monkeypatch):
         torch.testing.assert_close(f, s_, msg=name, **tol)
 
 
+def _knob_vs_default(knob, n, nk, causal, dtype, monkeypatch):
+    """(knob=1 grads, default-plan grads) on one seeded input.  S=328: two
+    256-row workgroups on each axis and a ragged tail that is a multiple
+    of neither 32 nor 64."""
+    b, s, d = 1, 328, 128
+    q = _rand(b, s, n, d, dtype, 121)
+    k = _rand(b, s, nk, d, dtype, 122)
+    v = _rand(b, s, nk, d, dtype, 123)
+    do = _rand(b, s, n, d, dtype, 124)
+    ext = _ext()
+    scale = 1.0 / math.sqrt(d)
+    o, lse = ext.attn_fwd(q, k, v, scale, causal)
+    delta = ext.attn_bwd_preprocess(o.to(dtype), do)
+    monkeypatch.setenv(knob, "1")
+    alt = ext.attn_bwd(do, q, k, v, delta, lse, scale, causal, True)
+    monkeypatch.delenv(knob)
+    base = ext.attn_bwd(do, q, k, v, delta, lse, scale, causal, True)
+    return dict(zip(("dq", "dk", "dv"), alt)), dict(zip(("dq", "dk", "dv"), base))
+
+
+# test_bwd_alt_plans_vs_split's gates for the same kernel pairs
+KNOB_TOL = {
+    torch.float16: dict(rtol=2e-3, atol=1e-3),
+    torch.bfloat16: dict(rtol=1e-2, atol=8e-3),
+}
+
+
+@pytest.mark.parametrize("causal", [False, True])
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+def test_bwd_dk_flip_vs_default(causal, dtype, monkeypatch):
+    """BA_BWD_DK_FLIP=1 swaps the split dK kernel for the flipped one and
+    nothing else: dq and dv come from the same atomic-free kernels."""
+    alt, base = _knob_vs_default("BA_BWD_DK_FLIP", 2, 2, causal, dtype,
+                                 monkeypatch)
+    assert torch.equal(alt["dq"], base["dq"]), "dq changed"
+    assert torch.equal(alt["dv"], base["dv"]), "dv changed"
+    torch.testing.assert_close(alt["dk"], base["dk"], **KNOB_TOL[dtype])
+
+
+@pytest.mark.parametrize("n,nk", [(2, 2), (4, 2)])
+@pytest.mark.parametrize("causal", [False, True])
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+def test_bwd_dq_pipe_vs_default(n, nk, causal, dtype, monkeypatch):
+    """BA_DQ_PIPE=1 swaps the dq kernel for its DQP=1 form and nothing
+    else.  N=4/Nk=2: the DQP=1 kernel indexes K/V by n / G too."""
+    alt, base = _knob_vs_default("BA_DQ_PIPE", n, nk, causal, dtype,
+                                 monkeypatch)
+    assert torch.equal(alt["dk"], base["dk"]), "dk changed"
+    assert torch.equal(alt["dv"], base["dv"]), "dv changed"
+    torch.testing.assert_close(alt["dq"], base["dq"], **KNOB_TOL[dtype])
+
+
+def test_bwd_rejects_unknown_plan(monkeypatch):
+    """A BA_BWD_FUSED value outside {0,1,2} fails naming the knob instead
+    of silently running the default plan."""
+    b, s, n, d = 1, 256, 2, 128
+    dtype = torch.float16
+    q = _rand(b, s, n, d, dtype, 131)
+    k = _rand(b, s, n, d, dtype, 132)
+    v = _rand(b, s, n, d, dtype, 133)
+    do = _rand(b, s, n, d, dtype, 134)
+    ext = _ext()
+    scale = 1.0 / math.sqrt(d)
+    o, lse = ext.attn_fwd(q, k, v, scale, False)
+    delta = ext.attn_bwd_preprocess(o.to(dtype), do)
+    monkeypatch.setenv("BA_BWD_FUSED", "3")
+    with pytest.raises(RuntimeError, match="BA_BWD_FUSED=3"):
+        ext.attn_bwd(do, q, k, v, delta, lse, scale, False, True)
+
+
 @pytest.mark.parametrize("det", [False, True])
 def test_bwd_accum_strided_views(det):
     """bwd_accum ADDS into strided accumulator views (the zigzag

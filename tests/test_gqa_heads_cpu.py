@@ -3,7 +3,7 @@
 
 The header is host-only, so a plain C++ compiler builds it with a small
 main (the pattern of tests/test_fwd_variant_table_cpu.py).  ba_gqa_group is
-what fwd_entry and launch_bwd call to validate (N, Nk) and derive G; 0 is
+what fwd_entry and bahip_attn_bwd_gqa call to validate (N, Nk) and derive G; 0 is
 the value they turn into BAHIP_ERR_UNSUPPORTED.
 """
 

@@ -8,7 +8,6 @@
 #include "../burst_attn_amd/csrc/attn_bwd.hip"
 
 #include <stdio.h>
-#include <vector>
 
 #define CK(x)                                                        \
   do {                                                               \
@@ -37,7 +36,7 @@ int main(int argc, char** argv) {
   using T = _Float16;
   const size_t nel = (size_t)B * S * N * D;
   T *q, *k, *v, *dout;
-  float *delta, *lse, *dq, *dk;
+  float *delta, *lse, *dq, *dk, *dv2;
   CK(hipMalloc(&q, nel * 2));
   CK(hipMalloc(&k, nel * 2));
   CK(hipMalloc(&v, nel * 2));
@@ -46,6 +45,7 @@ int main(int argc, char** argv) {
   CK(hipMalloc(&lse, (size_t)B * N * S * 4));
   CK(hipMalloc(&dq, nel * 4));
   CK(hipMalloc(&dk, nel * 4));
+  CK(hipMalloc(&dv2, nel * 4));
   int thr = 256;
   fill_kernel<<<(nel + thr - 1) / thr, thr>>>(q, nel, 1);
   fill_kernel<<<(nel + thr - 1) / thr, thr>>>(k, nel, 2);
@@ -56,23 +56,32 @@ int main(int argc, char** argv) {
   fillf_kernel<<<(nml + thr - 1) / thr, thr>>>(lse, nml, 11.f);
   CK(hipMemset(dq, 0, nel * 4));
   CK(hipMemset(dk, 0, nel * 4));
+  CK(hipMemset(dv2, 0, nel * 4));
   CK(hipDeviceSynchronize());
 
+  // attn_bwd.hip's own argument structs: dense tensors, non-causal, G = 1
   const float scale = 0.0883883f;
-  int64_t s4[3] = {(int64_t)S * N * D, (int64_t)N * D, (int64_t)D};
-  int64_t s2[2] = {(int64_t)N * S, (int64_t)S};
-  dim3 gdkq((unsigned)N, (unsigned)((S + 255) / 256), 1);
-  dim3 gkv((unsigned)((S + 255) / 256), (unsigned)N, 1);
-  dim3 gdq((unsigned)((S + 255) / 256), (unsigned)N, 1);
-
-  float* dv2;
-  CK(hipMalloc(&dv2, nel * 4));
-  CK(hipMemset(dv2, 0, nel * 4));
-#define DKQ_A                                                              \
-  dout, q, k, v, delta, lse, dq, dk, dv2, S, S, N, s4[0], s4[1], s4[2],    \
-      s4[0], s4[1], s4[2], s4[0], s4[1], s4[2], s4[0], s4[1], s4[2],       \
-      s2[0], s2[1], s2[0], s2[1], s4[0], s4[1], s4[2], s4[0], s4[1],       \
-      s4[2], s4[0], s4[1], s4[2], scale, 0
+  const int64_t sb = (int64_t)S * N * D, ss = (int64_t)N * D, sh = D;
+  const int64_t lb = (int64_t)N * S, lh = S;
+  auto inputs = [&](auto& a) {  // the fields all three structs share
+    a.dout = dout, a.q = q, a.k = k, a.v = v, a.delta = delta, a.lse = lse;
+    a.Sq = a.Sk = S, a.N = N, a.scale = scale, a.causal = 0;
+    a.g_sb = a.q_sb = a.k_sb = a.v_sb = sb;
+    a.g_ss = a.q_ss = a.k_ss = a.v_ss = ss;
+    a.g_sh = a.q_sh = a.k_sh = a.v_sh = sh;
+    a.d_sb = a.l_sb = lb, a.d_sh = a.l_sh = lh;
+  };
+  bwd_dkq_args dkqa = {};
+  inputs(dkqa);
+  dkqa.dq = dq, dkqa.dk = dk, dkqa.dv = dv2;
+  dkqa.dq_sb = dkqa.dk_sb = dkqa.dv_sb = sb;
+  dkqa.dq_ss = dkqa.dk_ss = dkqa.dv_ss = ss;
+  dkqa.dq_sh = dkqa.dk_sh = dkqa.dv_sh = sh;
+  bwd_dkv_args dkva = {};
+  inputs(dkva);
+  dkva.G = 1, dkva.out = dk, dkva.o_sb = sb, dkva.o_ss = ss, dkva.o_sh = sh;
+  bwd_dq_args dqa = dkva;
+  dqa.out = dq;
 
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
@@ -95,56 +104,18 @@ int main(int argc, char** argv) {
     printf("%-28s %8.2f ms\n", name, ms / 2);
   };
 
-  bench("dkq FUSE0 (flip dK)", [&] {
-    bwd_dkq_kernel<T, 128, 0, 0, 64><<<gdkq, 512>>>(DKQ_A);
-  });
-  bench("dkq FUSE1 DBG0 (full)", [&] {
-    bwd_dkq_kernel<T, 128, 1, 0, 64><<<gdkq, 512>>>(DKQ_A);
-  });
-  bench("dkq FUSE1 DBG1 (noGlbAtom)", [&] {
-    bwd_dkq_kernel<T, 128, 1, 1, 64><<<gdkq, 512>>>(DKQ_A);
-  });
-  bench("dkq FUSE1 DBG2 (dsWrite)", [&] {
-    bwd_dkq_kernel<T, 128, 1, 2, 64><<<gdkq, 512>>>(DKQ_A);
-  });
-  bench("dkq FUSE1 DBG3 (no dQ sec)", [&] {
-    bwd_dkq_kernel<T, 128, 1, 3, 64><<<gdkq, 512>>>(DKQ_A);
-  });
-  bench("dkq FUSE1 DBG4 (no KT rd)", [&] {
-    bwd_dkq_kernel<T, 128, 1, 4, 64><<<gdkq, 512>>>(DKQ_A);
-  });
-  bench("dkq FUSE1 DBG5 (no reduce)", [&] {
-    bwd_dkq_kernel<T, 128, 1, 5, 64><<<gdkq, 512>>>(DKQ_A);
-  });
-  bench("dkq FUSE1 DBG0 SCRW32", [&] {
-    bwd_dkq_kernel<T, 128, 1, 0, 32><<<gdkq, 512>>>(DKQ_A);
-  });
-  bench("dkvf (fused dK+dV)", [&] {
-    bwd_dkq_kernel<T, 128, 0, 0, 32, 1><<<gdkq, 512>>>(DKQ_A);
-  });
-  bench("dkv MODE1 (split dK)", [&] {
-    bwd_dkv_kernel<T, 128, 1, 64><<<gkv, 512>>>(
-        dout, q, k, v, delta, lse, dk, nullptr, S, S, N, s4[0], s4[1], s4[2],
-        s4[0], s4[1], s4[2], s4[0], s4[1], s4[2], s4[0], s4[1], s4[2], s2[0],
-        s2[1], s2[0], s2[1], s4[0], s4[1], s4[2], scale, 0);
-  });
-  bench("dkv MODE0 (dV)", [&] {
-    bwd_dkv_kernel<T, 128, 0, 64><<<gkv, 512>>>(
-        dout, q, k, v, delta, lse, dk, nullptr, S, S, N, s4[0], s4[1], s4[2],
-        s4[0], s4[1], s4[2], s4[0], s4[1], s4[2], s4[0], s4[1], s4[2], s2[0],
-        s2[1], s2[0], s2[1], s4[0], s4[1], s4[2], scale, 0);
-  });
-  bench("dq kernel DQP=1", [&] {
-    bwd_dq_kernel<T, 128, 1><<<gdq, 512>>>(
-        dout, q, k, v, delta, lse, dq, S, S, N, s4[0], s4[1], s4[2], s4[0],
-        s4[1], s4[2], s4[0], s4[1], s4[2], s4[0], s4[1], s4[2], s2[0], s2[1],
-        s2[0], s2[1], s4[0], s4[1], s4[2], scale, 0);
-  });
-  bench("dq kernel", [&] {
-    bwd_dq_kernel<T, 128><<<gdq, 512>>>(
-        dout, q, k, v, delta, lse, dq, S, S, N, s4[0], s4[1], s4[2], s4[0],
-        s4[1], s4[2], s4[0], s4[1], s4[2], s4[0], s4[1], s4[2], s2[0], s2[1],
-        s2[0], s2[1], s4[0], s4[1], s4[2], scale, 0);
-  });
+  bench("dkq FUSE0 (flip dK)", [&] { launch_dkq<T, 128, 0, 0, 64>(dkqa, B, 0); });
+  bench("dkq FUSE1 DBG0 (full)", [&] { launch_dkq<T, 128, 1, 0, 64>(dkqa, B, 0); });
+  bench("dkq FUSE1 DBG1 (noGlbAtom)", [&] { launch_dkq<T, 128, 1, 1, 64>(dkqa, B, 0); });
+  bench("dkq FUSE1 DBG2 (dsWrite)", [&] { launch_dkq<T, 128, 1, 2, 64>(dkqa, B, 0); });
+  bench("dkq FUSE1 DBG3 (no dQ sec)", [&] { launch_dkq<T, 128, 1, 3, 64>(dkqa, B, 0); });
+  bench("dkq FUSE1 DBG4 (no KT rd)", [&] { launch_dkq<T, 128, 1, 4, 64>(dkqa, B, 0); });
+  bench("dkq FUSE1 DBG5 (no reduce)", [&] { launch_dkq<T, 128, 1, 5, 64>(dkqa, B, 0); });
+  bench("dkq FUSE1 DBG0 SCRW32", [&] { launch_dkq<T, 128, 1, 0, 32>(dkqa, B, 0); });
+  bench("dkvf (fused dK+dV)", [&] { launch_dkq<T, 128, 0, 0, 32, 1>(dkqa, B, 0); });
+  bench("dkv MODE1 (split dK)", [&] { launch_dkv<T, 128, 1>(dkva, B, 0); });
+  bench("dkv MODE0 (dV)", [&] { launch_dkv<T, 128, 0>(dkva, B, 0); });
+  bench("dq kernel DQP=1", [&] { launch_dq<T, 128, 1>(dqa, B, 0); });
+  bench("dq kernel", [&] { launch_dq<T, 128, 0>(dqa, B, 0); });
   return 0;
 }
