@@ -28,18 +28,20 @@ convention).  K/V travel the ring UNEXPANDED (the forward payload and the
 comm buffers shrink N/Nk-fold), and ``k.grad``/``v.grad`` have Nk heads:
 the kernels sum each group's query heads in place.
 
-Causal load-balancing layouts (see oracle/partition.py):
-  * ``OpBurstAttn``     — zigzag: rank r holds global chunks [r] and
-    [2W-1-r]; per-round half-tile dispatch per ``:221-235`` (fwd) and
-    ``:303-367`` (bwd).
-  * ``OpBurstAttnStrip`` — striped: token t on rank t mod W; per-round
-    one-token shift per ``:459-475`` (fwd) and ``:557-585`` (bwd).
+The two causal load-balancing layouts (see oracle/partition.py) run the
+same code: ``OpBurstAttn`` (zigzag: rank r holds global chunks [r] and
+[2W-1-r]) and ``OpBurstAttnStrip`` (striped: token t on rank t mod W) only
+name their layout to ``_ring_forward`` / ``_ring_backward``.  All a layout
+decides is which rows of the two chunks a round computes, and that is
+``tile_window``; the travelling dq hops through ``_TravellingDq``.
 """
 
+import functools
 import math
 import os
 
 import torch
+import torch.distributed as dist
 
 from .comm import Ring, get_rank, replicate
 from .log_helper import get_logger
@@ -50,17 +52,15 @@ _logger = get_logger(__name__, level="WARN")
 __all__ = ["burst_attn_func", "burst_attn_func_striped", "OpBurstAttn", "OpBurstAttnStrip"]
 
 
-def get_partition_id(double_group, r):
-    """Source index of the K/V (fwd) or Q (bwd) chunk held at round r.
+def get_partition_id(double_group, r, process_group=None):
+    """Rank that owns the K/V (fwd) or Q (bwd) chunk held at round r.
 
-    Single ring: r-1 (equivalent to "source rank <= my rank" in the
-    causal dispatch).  Double ring: the source chunk's global rank, from
-    the intra/inter positions (reference burst_attn_interface.py:20-37).
+    Single ring: r-1 hops behind this rank.  Double ring: from the
+    intra/inter positions (reference burst_attn_interface.py:20-37).
     """
     if not double_group or double_group[0] is None:
-        return r - 1
-    import torch.distributed as dist
-
+        world = dist.get_world_size(process_group)
+        return (dist.get_rank(process_group) - (r - 1)) % world
     intra = dist.get_world_size(double_group[0])
     inter = dist.get_world_size(double_group[1])
     ii = dist.get_rank(double_group[0])
@@ -68,6 +68,36 @@ def get_partition_id(double_group, r):
     return ((ir - (r - 1) // intra) % inter) * intra + (
         (ii - (r - 1) % intra) % intra
     )
+
+
+_ALL = slice(None)
+
+
+def tile_window(layout, a, b, causal, s_local):
+    """What one ring round computes of the q chunk owned by rank ``a``
+    against the kv chunk owned by rank ``b``: ``(q_rows, kv_rows,
+    tile_causal)`` — two slices of the ``s_local`` local rows and the
+    causal flag of the tile itself.  Forward has a = this rank and b = the
+    source of the round's kv; backward a = the source of the round's q and
+    b = this rank.  The layouts are those of ``oracle/partition.py``."""
+    if layout == "zigzag" and causal:
+        assert s_local % 2 == 0, (
+            "zigzag causal needs an even per-rank seqlen (the rank holds "
+            "two half-chunks)"
+        )
+    if not causal or a == b:
+        return _ALL, _ALL, causal
+    if layout == "striped":
+        # local token i of rank r is global i*W + r: row i sees columns
+        # <= i of an earlier rank's kv, < i of a later rank's — the causal
+        # tile shifted by one token (reference :463-475, :557-585)
+        return (_ALL, _ALL, True) if b < a else (slice(1, None), slice(None, -1), True)
+    # zigzag, rank r holds global chunks [r] and [2W-1-r]: of an earlier
+    # rank's kv only chunk [b] is visible, to all of q (:225-231, :347-367);
+    # of a later rank's all is visible, to q's second half only (:232-235,
+    # :322-345)
+    half = s_local // 2
+    return (_ALL, slice(None, half), False) if b < a else (slice(half, None), _ALL, False)
 
 
 def _record_stream(*tensors):
@@ -170,17 +200,18 @@ def burst_attn_func_striped(
     )
 
 
-def _setup_ctx(ctx, q, softmax_scale, flash, causal, optimize_bwd_comm,
-               deterministic, process_group, double_group):
+def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
+                  causal=False, optimize_bwd_comm=False, deterministic=False,
+                  process_group=None, double_group=[None, None]):
+    """Forward of both layouts: q stays, {k, v} travel the ring."""
     _check_flash_arg(flash)
+    ctx.dq_group = double_group
     if isinstance(double_group[0], tuple):
         # [(group, dq_group), (group2, dq_group2)] — separate backward dq
         # ring groups (reference :188-194)
         ctx.dq_group = (double_group[0][1], double_group[1][1])
         double_group = (double_group[0][0], double_group[1][0])
-    else:
-        ctx.dq_group = None
-    ctx.softmax_scale = (
+    ctx.softmax_scale = scale = (
         1.0 / math.sqrt(q.shape[-1]) if softmax_scale is None else softmax_scale
     )
     ctx.causal = causal
@@ -188,323 +219,149 @@ def _setup_ctx(ctx, q, softmax_scale, flash, causal, optimize_bwd_comm,
     ctx.deterministic = deterministic
     ctx.process_group = process_group
     ctx.double_group = double_group
-    return double_group
 
-
-def _finalize_fwd(ctx, P, q, ori_k, ori_v, state):
+    P = get_tile_provider()
+    ring = Ring(process_group, double_group)
+    W, rank = ring.world_size, ring.rank
+    ori_k, ori_v = replicate(k), replicate(v)
+    comm_bufs = [torch.empty_like(k), torch.empty_like(v)]
+    state = None  # provider-owned carry-in accumulator (in-kernel merge)
+    record = []
+    for r in range(1, W + 1):
+        src = get_partition_id(double_group, r, process_group)
+        record.append(src)
+        qw, kw, tile_causal = tile_window(layout, rank, src, causal, q.shape[1])
+        if r != W:
+            ring.double_ring_send_recv([k, v], comm_bufs, r)
+            ring.commit()
+        state = P.fwd_accum(state, q[:, qw], k[:, kw], v[:, kw], scale,
+                            tile_causal, row_offset=qw.start or 0)
+        if r != W:
+            kv, comm_bufs = _record_stream(*comm_bufs), [k, v]
+            k, v = kv
+            ring.wait()
+    _logger.info("fwd record of rank %d: %s", get_rank(), record)
     # o in q.dtype, lse [B,N,S] fp32 (reference :250-252 semantics)
     out, lse = P.fwd_finalize(state, q.dtype)
     ctx.save_for_backward(q, ori_k, ori_v, lse, replicate(out))
     return out
 
 
+class _TravellingDq:
+    """The hop of the dq that follows its q chunk around ``ring``, in one
+    of two forms (``_dq_wire_dtype``): cast into a wire buffer, sent, and
+    copied back into the fp32 dq; or the fp32 dq itself sent and swapped
+    with the buffer it was received into."""
+
+    def __init__(self, ring, q, dq):
+        self.ring = ring
+        self.wire_dtype = _dq_wire_dtype(q, ring)
+        if self.wire_dtype is not None:
+            self.wire_s = torch.empty(q.shape, dtype=self.wire_dtype, device=q.device)
+            self.wire_r = torch.empty_like(self.wire_s)
+        else:
+            # the fp32 swap buffer is only needed on the fp32-wire path
+            self.buf = [torch.empty_like(dq)]
+
+    def start(self, dq, r):
+        """Queue and commit the hop of round ``r``."""
+        if self.wire_dtype is not None:
+            self.wire_s.copy_(dq)
+            self.ring.send_recv([self.wire_s], [self.wire_r])
+        else:
+            self.ring.double_ring_send_recv_q([dq], self.buf, r)
+        self.ring.commit()
+
+    def finish(self, dq):
+        """Wait for the hop; returns the dq that arrived."""
+        self.ring.wait()
+        if self.wire_dtype is not None:
+            dq.copy_(self.wire_r)
+            return dq
+        recv, self.buf = _record_stream(*self.buf), [dq]
+        return recv[0]
+
+
+def _ring_backward(layout, ctx, grad_output):
+    """Backward of both layouts: k, v, dk, dv stay; {delta-or-o,
+    grad_output, q, lse} travel one ring and their dq a second one."""
+    q, k, v, lse, o = ctx.saved_tensors
+    P = get_tile_provider()
+    scale, causal = ctx.softmax_scale, ctx.causal
+    grad_output = grad_output.contiguous()
+    group, double_group = ctx.process_group, ctx.double_group
+    ring = Ring(group, double_group)
+    dq_ring = Ring(group, ctx.dq_group)
+    W, rank = ring.world_size, ring.rank
+
+    dq = torch.zeros(q.shape, dtype=torch.float32, device=q.device)
+    dk = torch.zeros(k.shape, dtype=torch.float32, device=k.device)
+    dv = torch.zeros(v.shape, dtype=torch.float32, device=v.device)
+    # rank-local staging for rounds whose travelling dq is in flight:
+    # kernels accumulate here during the hop, ONE add folds it in
+    # after the wait (at W=1 the kernels hit dq directly)
+    dq_local = torch.zeros_like(dq) if W > 1 else dq
+
+    if ctx.optimize_bwd_comm:
+        # ring the tiny fp32 delta instead of o (reference :269-278)
+        dlt = P.bwd_preprocess(o, grad_output)  # [B,N,S] fp32
+        delta_buf = None
+    else:
+        dlt = o  # o travels; delta recomputed per round
+        delta_buf = torch.empty(
+            q.shape[0], q.shape[2], q.shape[1], dtype=torch.float32,
+            device=q.device,
+        )
+    dq_hop = _TravellingDq(dq_ring, q, dq)
+    read_bufs = [torch.empty_like(t) for t in (dlt, grad_output, q, lse)]
+    for r in range(1, W + 1):
+        src = get_partition_id(double_group, r, group)
+        qw, kw, tile_causal = tile_window(layout, src, rank, causal, q.shape[1])
+        if r != W:
+            ring.double_ring_send_recv([dlt, grad_output, q, lse], read_bufs, r)
+            ring.commit()
+        if r != 1:
+            dq_hop.start(dq, r)
+        delta = (
+            dlt if ctx.optimize_bwd_comm
+            else P.bwd_preprocess(dlt, grad_output, out=delta_buf)
+        )
+        tgt = dq if r == 1 else dq_local
+        P.bwd_accum(
+            grad_output[:, qw], q[:, qw], k[:, kw], v[:, kw],
+            delta[:, :, qw], lse[:, :, qw], scale, tile_causal,
+            ctx.deterministic, tgt[:, qw], dk[:, kw], dv[:, kw],
+        )
+        if r != W:
+            recv, read_bufs = (
+                _record_stream(*read_bufs),
+                [dlt, grad_output, q, lse],
+            )
+            dlt, grad_output, q, lse = recv
+        ring.wait()
+        if r != 1:
+            dq = dq_hop.finish(dq)
+            # fold this round's local contribution into the received dq
+            dq[:, qw] += dq_local[:, qw]
+            dq_local[:, qw].zero_()
+    # one extra hop returns the travelling dq to its owner (:393-396)
+    dq_hop.start(dq, W + 1)
+    dq = dq_hop.finish(dq)
+    return (
+        dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype),
+        None, None, None, None, None, None, None,
+    )
+
+
 class OpBurstAttn(torch.autograd.Function):
     """Zigzag (default) ring attention; q,k,v: [B, S/W, N, H]."""
 
-    @staticmethod
-    def forward(ctx, q, k, v, softmax_scale=None, flash="cuda", causal=False,
-                optimize_bwd_comm=False, deterministic=False,
-                process_group=None, double_group=[None, None]):
-        double_group = _setup_ctx(
-            ctx, q, softmax_scale, flash, causal, optimize_bwd_comm,
-            deterministic, process_group, double_group,
-        )
-        P = get_tile_provider()
-        scale = ctx.softmax_scale
-        ring = Ring(process_group, double_group)
-        W, rank = ring.world_size, ring.rank
-        ori_k, ori_v = replicate(k), replicate(v)
-        comm_bufs = [torch.empty_like(k), torch.empty_like(v)]
-        if causal:
-            assert q.shape[1] % 2 == 0, (
-                "zigzag causal needs an even per-rank seqlen (the rank holds "
-                "two half-chunks)"
-            )
-        half = q.shape[1] // 2
-        state = None  # provider-owned carry-in accumulator (in-kernel merge)
-        record = []
-        for r in range(1, W + 1):
-            offset = get_partition_id(double_group, r)
-            record.append(offset)
-            split_kv = offset <= rank  # kv origin precedes this rank's chunks
-            if r != W:
-                ring.double_ring_send_recv([k, v], comm_bufs, r)
-                ring.commit()
-            if r == 1 or not causal:
-                state = P.fwd_accum(state, q, k, v, scale, causal)
-            elif split_kv:
-                # kv chunks [src, 2W-1-src] with src < rank: only chunk
-                # [src] (first half) is attended, by all local q (:225-231)
-                state = P.fwd_accum(state, q, k[:, :half], v[:, :half], scale, False)
-            else:
-                # src > rank: only q's second half (chunk [2W-1-rank])
-                # attends, to the full received kv (:232-235)
-                state = P.fwd_accum(state, q[:, half:], k, v, scale, False,
-                                    row_offset=half)
-            if r != W:
-                kv, comm_bufs = _record_stream(*comm_bufs), [k, v]
-                k, v = kv
-                ring.wait()
-        _logger.info("fwd record of rank %d: %s", get_rank(), record)
-        return _finalize_fwd(ctx, P, q, ori_k, ori_v, state)
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        q, k, v, lse, o = ctx.saved_tensors
-        P = get_tile_provider()
-        scale = ctx.softmax_scale
-        grad_output = grad_output.contiguous()
-        group, double_group = ctx.process_group, ctx.double_group
-        ring = Ring(group, double_group)
-        dq_ring = Ring(group, ctx.dq_group if ctx.dq_group is not None else double_group)
-        W, rank = ring.world_size, ring.rank
-        if ctx.causal:
-            assert q.shape[1] % 2 == 0, (
-                "zigzag causal needs an even per-rank seqlen (the rank holds "
-                "two half-chunks)"
-            )
-        half = q.shape[1] // 2
-
-        dq = torch.zeros(q.shape, dtype=torch.float32, device=q.device)
-        dk = torch.zeros(k.shape, dtype=torch.float32, device=k.device)
-        dv = torch.zeros(v.shape, dtype=torch.float32, device=v.device)
-        # rank-local staging for rounds whose travelling dq is in flight:
-        # kernels accumulate here during the hop, ONE add folds it in
-        # after the wait (at W=1 the kernels hit dq directly)
-        dq_local = torch.zeros_like(dq) if W > 1 else dq
-
-        if ctx.optimize_bwd_comm:
-            # ring the tiny fp32 delta instead of o (reference :269-278)
-            dlt = P.bwd_preprocess(o, grad_output)  # [B,N,S] fp32
-            delta_buf = None
-        else:
-            dlt = o  # o travels; delta recomputed per round
-            delta_buf = torch.empty(
-                q.shape[0], q.shape[2], q.shape[1], dtype=torch.float32,
-                device=q.device,
-            )
-        wire_dtype = _dq_wire_dtype(q, dq_ring)
-        if wire_dtype is not None:
-            wire_s = torch.empty(q.shape, dtype=wire_dtype, device=q.device)
-            wire_r = torch.empty_like(wire_s)
-
-        read_bufs = [torch.empty_like(t) for t in (dlt, grad_output, q, lse)]
-        # the fp32 swap buffer is only needed on the fp32-wire path
-        dq_buf = [torch.empty_like(dq)] if wire_dtype is None else []
-        for r in range(1, W + 1):
-            offset = get_partition_id(double_group, r)
-            split_q = offset <= rank  # q origin precedes this rank
-            if r != W:
-                ring.double_ring_send_recv([dlt, grad_output, q, lse], read_bufs, r)
-                ring.commit()
-            if r != 1:
-                if wire_dtype is not None:
-                    wire_s.copy_(dq)
-                    dq_ring.send_recv([wire_s], [wire_r])
-                else:
-                    dq_ring.double_ring_send_recv_q([dq], dq_buf, r)
-                dq_ring.commit()
-            delta = (
-                dlt if ctx.optimize_bwd_comm
-                else P.bwd_preprocess(dlt, grad_output, out=delta_buf)
-            )
-            tgt = dq if r == 1 else dq_local
-            if r == 1 or not ctx.causal:
-                P.bwd_accum(
-                    grad_output, q, k, v, delta, lse, scale, ctx.causal,
-                    ctx.deterministic, tgt, dk, dv,
-                )
-                acc = "full"
-            elif split_q:
-                # travelling q's second half attends my full kv (:322-345)
-                P.bwd_accum(
-                    grad_output[:, half:], q[:, half:], k, v,
-                    delta[:, :, half:], lse[:, :, half:], scale, False,
-                    ctx.deterministic, tgt[:, half:], dk, dv,
-                )
-                acc = "q_half"
-            else:
-                # travelling q (all of it) attends only my kv first half
-                # (:347-367)
-                P.bwd_accum(
-                    grad_output, q, k[:, :half], v[:, :half], delta, lse,
-                    scale, False, ctx.deterministic,
-                    tgt, dk[:, :half], dv[:, :half],
-                )
-                acc = "kv_half"
-            if r != W:
-                recv, read_bufs = (
-                    _record_stream(*read_bufs),
-                    [dlt, grad_output, q, lse],
-                )
-                dlt, grad_output, q, lse = recv
-            ring.wait()
-            if r != 1:
-                dq_ring.wait()
-                if wire_dtype is not None:
-                    dq.copy_(wire_r)
-                else:
-                    recv, dq_buf = _record_stream(*dq_buf), [dq]
-                    dq = recv[0]
-                # fold this round's local contribution into the received dq
-                if acc == "q_half":
-                    dq[:, half:] += dq_local[:, half:]
-                    dq_local[:, half:].zero_()
-                else:
-                    dq += dq_local
-                    dq_local.zero_()
-        # one extra hop returns the travelling dq to its owner (:393-396)
-        if wire_dtype is not None:
-            wire_s.copy_(dq)
-            dq_ring.send_recv([wire_s], [wire_r])
-            dq_ring.commit()
-            dq_ring.wait()
-            dq.copy_(wire_r)
-        else:
-            dq_ring.double_ring_send_recv_q([dq], dq_buf, W + 1)
-            dq_ring.commit()
-            dq_ring.wait()
-            dq = _record_stream(*dq_buf)[0]
-        return (
-            dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype),
-            None, None, None, None, None, None, None,
-        )
+    forward = staticmethod(functools.partial(_ring_forward, "zigzag"))
+    backward = staticmethod(functools.partial(_ring_backward, "zigzag"))
 
 
 class OpBurstAttnStrip(torch.autograd.Function):
     """Striped ring attention (token t → rank t mod W); q,k,v [B,S/W,N,H]."""
 
-    @staticmethod
-    def forward(ctx, q, k, v, softmax_scale=None, flash="cuda", causal=False,
-                optimize_bwd_comm=False, deterministic=False,
-                process_group=None, double_group=[None, None]):
-        double_group = _setup_ctx(
-            ctx, q, softmax_scale, flash, causal, optimize_bwd_comm,
-            deterministic, process_group, double_group,
-        )
-        P = get_tile_provider()
-        scale = ctx.softmax_scale
-        ring = Ring(process_group, double_group)
-        W, rank = ring.world_size, ring.rank
-        ori_k, ori_v = replicate(k), replicate(v)
-        comm_bufs = [torch.empty_like(k), torch.empty_like(v)]
-        state = None
-        for r in range(1, W + 1):
-            offset = get_partition_id(double_group, r)
-            causal_shift = offset > rank  # kv origin follows this rank
-            if r != W:
-                ring.double_ring_send_recv([k, v], comm_bufs, r)
-                ring.commit()
-            if not causal_shift or not causal:
-                state = P.fwd_accum(state, q, k, v, scale, causal)
-            else:
-                # one-token shift: striped causal vs a later rank's kv
-                # (:463-475)
-                state = P.fwd_accum(state, q[:, 1:], k[:, :-1], v[:, :-1],
-                                    scale, causal, row_offset=1)
-            if r != W:
-                kv, comm_bufs = _record_stream(*comm_bufs), [k, v]
-                k, v = kv
-                ring.wait()
-        return _finalize_fwd(ctx, P, q, ori_k, ori_v, state)
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        q, k, v, lse, o = ctx.saved_tensors
-        P = get_tile_provider()
-        scale = ctx.softmax_scale
-        grad_output = grad_output.contiguous()
-        group, double_group = ctx.process_group, ctx.double_group
-        ring = Ring(group, double_group)
-        dq_ring = Ring(group, ctx.dq_group if ctx.dq_group is not None else double_group)
-        W, rank = ring.world_size, ring.rank
-
-        dq = torch.zeros(q.shape, dtype=torch.float32, device=q.device)
-        dk = torch.zeros(k.shape, dtype=torch.float32, device=k.device)
-        dv = torch.zeros(v.shape, dtype=torch.float32, device=v.device)
-        dq_local = torch.zeros_like(dq) if W > 1 else dq
-
-        if ctx.optimize_bwd_comm:
-            dlt = P.bwd_preprocess(o, grad_output)
-            delta_buf = None
-        else:
-            dlt = o
-            delta_buf = torch.empty(
-                q.shape[0], q.shape[2], q.shape[1], dtype=torch.float32,
-                device=q.device,
-            )
-        wire_dtype = _dq_wire_dtype(q, dq_ring)
-        if wire_dtype is not None:
-            wire_s = torch.empty(q.shape, dtype=wire_dtype, device=q.device)
-            wire_r = torch.empty_like(wire_s)
-
-        read_bufs = [torch.empty_like(t) for t in (dlt, grad_output, q, lse)]
-        # the fp32 swap buffer is only needed on the fp32-wire path
-        dq_buf = [torch.empty_like(dq)] if wire_dtype is None else []
-        for r in range(1, W + 1):
-            offset = get_partition_id(double_group, r)
-            causal_shift = offset <= rank and r != 1  # q origin precedes
-            if r != W:
-                ring.double_ring_send_recv([dlt, grad_output, q, lse], read_bufs, r)
-                ring.commit()
-            if r != 1:
-                if wire_dtype is not None:
-                    wire_s.copy_(dq)
-                    dq_ring.send_recv([wire_s], [wire_r])
-                else:
-                    dq_ring.double_ring_send_recv_q([dq], dq_buf, r)
-                dq_ring.commit()
-            delta = (
-                dlt if ctx.optimize_bwd_comm
-                else P.bwd_preprocess(dlt, grad_output, out=delta_buf)
-            )
-            tgt = dq if r == 1 else dq_local
-            if not causal_shift or not ctx.causal:
-                P.bwd_accum(
-                    grad_output, q, k, v, delta, lse, scale, ctx.causal,
-                    ctx.deterministic, tgt, dk, dv,
-                )
-                shifted = False
-            else:
-                # shifted tile: q[1:] vs k[:-1] (reference :557-585)
-                P.bwd_accum(
-                    grad_output[:, 1:], q[:, 1:], k[:, :-1], v[:, :-1],
-                    delta[:, :, 1:], lse[:, :, 1:], scale, ctx.causal,
-                    ctx.deterministic, tgt[:, 1:], dk[:, :-1], dv[:, :-1],
-                )
-                shifted = True
-            if r != W:
-                recv, read_bufs = (
-                    _record_stream(*read_bufs),
-                    [dlt, grad_output, q, lse],
-                )
-                dlt, grad_output, q, lse = recv
-            ring.wait()
-            if r != 1:
-                dq_ring.wait()
-                if wire_dtype is not None:
-                    dq.copy_(wire_r)
-                else:
-                    recv, dq_buf = _record_stream(*dq_buf), [dq]
-                    dq = recv[0]
-                if shifted:
-                    dq[:, 1:] += dq_local[:, 1:]
-                    dq_local[:, 1:].zero_()
-                else:
-                    dq += dq_local
-                    dq_local.zero_()
-        if wire_dtype is not None:
-            wire_s.copy_(dq)
-            dq_ring.send_recv([wire_s], [wire_r])
-            dq_ring.commit()
-            dq_ring.wait()
-            dq.copy_(wire_r)
-        else:
-            dq_ring.double_ring_send_recv_q([dq], dq_buf, W + 1)
-            dq_ring.commit()
-            dq_ring.wait()
-            dq = _record_stream(*dq_buf)[0]
-        return (
-            dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype),
-            None, None, None, None, None, None, None,
-        )
+    forward = staticmethod(functools.partial(_ring_forward, "striped"))
+    backward = staticmethod(functools.partial(_ring_backward, "striped"))

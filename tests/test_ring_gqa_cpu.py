@@ -14,83 +14,57 @@ import os
 
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from oracle.partition import get_chunk
 
+from .gloo_ranks import run_ranks
 from .test_ring_cpu import ATOL, RTOL
 
 
-def _worker(rank, world, port, causal, striped, optimize_bwd_comm, nk, fail_q):
-    try:
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-        from burst_attn_amd.tile import _set_tile_provider_for_testing
-        from burst_attn_amd import burst_attn_func, burst_attn_func_striped
-        from .gqa_cpu_provider import GqaOracleTileProvider, gqa_full_reference
+def _worker(rank, world, causal, striped, optimize_bwd_comm, nk):
+    from burst_attn_amd.tile import _set_tile_provider_for_testing
+    from burst_attn_amd import burst_attn_func, burst_attn_func_striped
+    from .gqa_cpu_provider import GqaOracleTileProvider, gqa_full_reference
 
-        P = GqaOracleTileProvider()
-        _set_tile_provider_for_testing(P)
+    P = GqaOracleTileProvider()
+    _set_tile_provider_for_testing(P)
 
-        b, s_local, n, d = 2, 64, 4, 64
-        s = s_local * world
-        g = torch.Generator().manual_seed(20250611)
-        q = torch.randn(b, s, n, d, generator=g)
-        k = torch.randn(b, s, nk, d, generator=g)
-        v = torch.randn(b, s, nk, d, generator=g)
-        do = torch.randn(b, s, n, d, generator=g)
+    b, s_local, n, d = 2, 64, 4, 64
+    s = s_local * world
+    g = torch.Generator().manual_seed(20250611)
+    q = torch.randn(b, s, n, d, generator=g)
+    k = torch.randn(b, s, nk, d, generator=g)
+    v = torch.randn(b, s, nk, d, generator=g)
+    do = torch.randn(b, s, n, d, generator=g)
 
-        o_ref, dq_ref, dk_ref, dv_ref = gqa_full_reference(q, k, v, do, None,
-                                                           causal)
+    o_ref, dq_ref, dk_ref, dv_ref = gqa_full_reference(q, k, v, do, None,
+                                                       causal)
 
-        zig = causal and not striped
-        ch = lambda t: get_chunk(t, 1, rank, world, zigzag=zig, striped=striped)
-        qc = ch(q).requires_grad_()
-        kc = ch(k).requires_grad_()
-        vc = ch(v).requires_grad_()
-        func = burst_attn_func_striped if striped else burst_attn_func
-        o = func(qc, kc, vc, None, "cuda", causal, optimize_bwd_comm, False)
-        dq, dk, dv = torch.autograd.grad(o, (qc, kc, vc), ch(do))
+    zig = causal and not striped
+    ch = lambda t: get_chunk(t, 1, rank, world, zigzag=zig, striped=striped)
+    qc = ch(q).requires_grad_()
+    kc = ch(k).requires_grad_()
+    vc = ch(v).requires_grad_()
+    func = burst_attn_func_striped if striped else burst_attn_func
+    o = func(qc, kc, vc, None, "cuda", causal, optimize_bwd_comm, False)
+    dq, dk, dv = torch.autograd.grad(o, (qc, kc, vc), ch(do))
 
-        assert dk.shape == kc.shape and dv.shape == vc.shape
-        assert dq.shape == qc.shape
-        torch.testing.assert_close(o, ch(o_ref), rtol=RTOL, atol=ATOL)
-        torch.testing.assert_close(dv, ch(dv_ref), rtol=RTOL, atol=ATOL)
-        torch.testing.assert_close(dk, ch(dk_ref), rtol=RTOL, atol=ATOL)
-        torch.testing.assert_close(dq, ch(dq_ref), rtol=RTOL, atol=ATOL)
-        # unexpanded on the wire: one tile call per round, and the K/V of
-        # every round after the first (received over the ring) has Nk heads
-        assert len(P.fwd_kv_heads) == world and len(P.bwd_kv_heads) == world
-        assert all(h == (nk, nk) for h in P.fwd_kv_heads[1:]), P.fwd_kv_heads
-        assert all(h == (nk, nk) for h in P.bwd_kv_heads), P.bwd_kv_heads
-        dist.destroy_process_group()
-    except Exception as e:  # surface the real failure to the parent
-        fail_q.put(f"rank {rank}: {type(e).__name__}: {e}")
-        raise
-
-
-_PORT = [29651]
+    assert dk.shape == kc.shape and dv.shape == vc.shape
+    assert dq.shape == qc.shape
+    torch.testing.assert_close(o, ch(o_ref), rtol=RTOL, atol=ATOL)
+    torch.testing.assert_close(dv, ch(dv_ref), rtol=RTOL, atol=ATOL)
+    torch.testing.assert_close(dk, ch(dk_ref), rtol=RTOL, atol=ATOL)
+    torch.testing.assert_close(dq, ch(dq_ref), rtol=RTOL, atol=ATOL)
+    # unexpanded on the wire: one tile call per round, and the K/V of
+    # every round after the first (received over the ring) has Nk heads
+    assert len(P.fwd_kv_heads) == world and len(P.bwd_kv_heads) == world
+    assert all(h == (nk, nk) for h in P.fwd_kv_heads[1:]), P.fwd_kv_heads
+    assert all(h == (nk, nk) for h in P.bwd_kv_heads), P.bwd_kv_heads
 
 
 def _spawn(world, causal, striped, optimize_bwd_comm, nk):
-    _PORT[0] += 1
-    ctx = mp.get_context("spawn")
-    fail_q = ctx.SimpleQueue()
-    try:
-        mp.spawn(
-            _worker,
-            args=(world, _PORT[0], causal, striped, optimize_bwd_comm, nk,
-                  fail_q),
-            nprocs=world,
-            join=True,
-        )
-    except Exception:
-        msgs = []
-        while not fail_q.empty():
-            msgs.append(fail_q.get())
-        raise AssertionError("GQA ring test failed:\n" + "\n".join(msgs))
+    run_ranks(_worker, world, causal, striped, optimize_bwd_comm, nk,
+              what="GQA ring")
 
 
 @pytest.mark.parametrize("optimize_bwd_comm", [False, True])
