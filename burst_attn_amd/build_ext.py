@@ -15,7 +15,7 @@ BUILD = os.path.join(PKG_DIR, "csrc", "_build")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-DEVICE_SOURCES = ["attn_fwd.hip", "attn_bwd.hip"]
+DEVICE_SOURCES = ["attn_fwd.hip", "attn_bwd.hip", "probes.hip"]
 HOST_SOURCES = ["ext_torch.cpp"]
 
 
@@ -62,7 +62,7 @@ def build(verbose=True, force=False):
         sp = os.path.join(CSRC, src)
         op = os.path.join(BUILD, src.replace(".cpp", ".o"))
         objs.append(op)
-        if force or _newer(sp, op) or _newer(abihdr, op):
+        if force or _newer(sp, op) or any(_newer(h, op) for h in hdrs):
             cmd = [
                 HIPCC, *common,
                 f"-D_GLIBCXX_USE_CXX11_ABI={abi}",

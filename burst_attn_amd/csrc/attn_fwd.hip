@@ -30,6 +30,20 @@
 
 namespace {
 
+// Buffer index of one tile-loop copy: a compile-time literal (ba_ic) in the
+// loop unrolled by the buffer period, a runtime value (ba_dyn) in the rolled
+// one.
+template <int N>
+struct ba_ic {
+  static constexpr int value = N;
+};
+struct ba_dyn {
+  int value;
+};
+template <int N>
+__device__ __forceinline__ int ba_buf_of(ba_ic<N>) { return N; }
+__device__ __forceinline__ int ba_buf_of(ba_dyn d) { return d.value; }
+
 // OUT_STATE=0: write normalised o (fp32) + lse — the stateless tile.
 // OUT_STATE=1: carry-in/carry-out accumulator state (acc = unnormalised
 // O, m = running max in the exp2 domain, l = running sum) — the fused
@@ -73,17 +87,6 @@ namespace {
 // t+1's buffer two tiles ago and a barrier every tile orders it.  The
 // QK cluster's lgkm park (SQ_WAIT_ANY 38% in the r2 PMC taxonomy)
 // becomes overlap.  Requires SUBT=1, NBUF=4, VPATH=0.
-template <int N>
-struct ba_ic {
-  static constexpr int value = N;
-};
-struct ba_dyn {
-  int value;
-};
-template <int N>
-__device__ __forceinline__ int ba_buf_of(ba_ic<N>) { return N; }
-__device__ __forceinline__ int ba_buf_of(ba_dyn d) { return d.value; }
-
 template <typename T, int D, int KVBLK, int OUT_STATE, int VPATH, int SUBT,
           int NT = 512, int NBUF = 2, int KREG = 0>
 __global__ __launch_bounds__(NT) void attn_fwd_kernel(
@@ -172,26 +175,69 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
   const int nt = (kv_limit + KVBLK - 1) / KVBLK;
   static_assert(SUBT != 2 || (NBUF == 4 && VPATH == 0),
                 "the T15 pipeline needs NBUF=4 and the V^T image");
+  static_assert(SUBT != 3 || (NBUF == 4 && VPATH == 0 && NT == 256),
+                "SUBT=3: NT=256 (1 wave/SIMD), NBUF=4, V^T image");
 
-  // ---- SUBT=2 pipeline state: the previous subtile's raw scores and
-  // its metadata, finished during the next subtile's QK cluster
-  f32x16_t stP;
-  int p_kv0 = -1;   // -1 = pipeline empty
-  int p_cur = 0;
-  bool p_full = false;
-  constexpr float DEFER_THR2 = 8.f;
-  auto finish_subtile = [&]() {
-    if (!p_full) {
+  // ---- the steps, one definition each: every SUBT/KREG body below is a
+  // sequence of these.  Always inlined, so a body compiles as if the steps
+  // were written out in it; their shapes (what is a parameter, where a loop
+  // sits) are the ones that leave the default variant's code as it was,
+  // see profiles/fwd_kernel/README.md before reshaping one.
+#define BA_STEP __attribute__((always_inline))
+  // K fragment s (A operand of S^T) of the 32-kv subtile (buf, kvs)
+  auto k_frag = [&](int buf, int kvs, int s) BA_STEP {
+    return ba_ld_rowslice<T, D, SWZ_K>(ldsK(buf), kvs * 32 + l31,
+                                       16 * s + 8 * hi);
+  };
+  auto load_kfrags = [&](int buf, int kvs, frag* kf) BA_STEP {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int kv_g = p_kv0 + ba_crow(r, 0) + 4 * hi;
-        if (!(kv_g < Sk && (!causal || kv_g <= q_row))) stP[r] = BA_NEG_BIG;
-      }
+    for (int s = 0; s < D / 16; ++s) kf[s] = k_frag(buf, kvs, s);
+  };
+  // ... of the subtile after (t, kvs): (t,0) -> (t,1) -> (t+1,0)
+  auto load_next_kfrags = [&](int t, int kvs, frag* kf) BA_STEP {
+    const int nt_t = (kvs == 0) ? t : t + 1;
+    if (nt_t < nt) load_kfrags(nt_t % NBUF, kvs ^ 1, kf);
+  };
+  // S^T = mfma(K, Q) of one subtile (raw, unscaled scores), K fragments
+  // from registers / each read from LDS right before its MFMA
+  auto qk_regs = [&](const frag* kf) BA_STEP {
+    f32x16_t s = (f32x16_t)(0.f);
+#pragma unroll
+    for (int i = 0; i < D / 16; ++i) s = MT::mma(kf[i], qf[i], s);
+    return s;
+  };
+  auto qk_lds = [&](int buf, int kvs) BA_STEP {
+    f32x16_t s = (f32x16_t)(0.f);
+#pragma unroll
+    for (int i = 0; i < D / 16; ++i)
+      s = MT::mma(k_frag(buf, kvs, i), qf[i], s);
+    return s;
+  };
+  // boundary mask of the subtile at kv rows [base + off, +32)
+  auto mask_sub = [&](f32x16_t& s, int base, int off) BA_STEP {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int kv_g = base + off + ba_crow(r, 0) + 4 * hi;
+      if (!(kv_g < Sk && (!causal || kv_g <= q_row))) s[r] = BA_NEG_BIG;
     }
-    float tm = ba_max16(stP);
+  };
+  // row max in the exp2 domain.  The softmax scale is folded into the exp
+  // argument (exp2+fma): the max is taken on RAW scores (max commutes with
+  // c2 > 0), the scale costs one multiply on the max instead of 16 per
+  // subtile
+  auto row_max2 = [&](const f32x16_t& s) BA_STEP {
+    float tm = ba_max16(s);
     tm = fmaxf(tm, __shfl_xor(tm, 32));
-    tm *= c2;
-    if (!__all(tm - m2 <= DEFER_THR2)) {
+    return tm * c2;
+  };
+  // online-softmax rescale (lane-local), defer-max (T13): skip the O/l
+  // rescale while the running max grows by <= THR (exp2 domain); P is then
+  // bounded by 2^THR instead of 1, which the fp32 accumulate absorbs.
+  // Decision taken BEFORE these scores are exponentiated (the
+  // textbook-safe order); wave-uniform.
+  constexpr float DEFER_THR = 8.f;
+  auto rescale = [&](float tm) BA_STEP {
+    if (!__all(tm - m2 <= DEFER_THR)) {
       const float mnew = fmaxf(m2, tm);
       const float alpha = ba_exp2(m2 - mnew);
       m2 = mnew;
@@ -201,33 +247,78 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) ot[dt][r] *= alpha;
     }
+  };
+  // the rest of a subtile's softmax once its max is known: rescale, exp2
+  // with the row sum, P -> fragments
+  auto softmax_tail = [&](f32x16_t& s, float tm, frag* pf) BA_STEP {
+    rescale(tm);
     float rowsum = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      stP[r] = ba_exp2(__builtin_fmaf(stP[r], c2, -m2));
-      rowsum += stP[r];
+      s[r] = ba_exp2(__builtin_fmaf(s[r], c2, -m2));
+      rowsum += s[r];
     }
     rowsum += __shfl_xor(rowsum, 32);
     lsum += rowsum;
-    frag pfp[2];
-    ba_build_frag_pair<T>(stP, pfp);
+    ba_build_frag_pair<T>(s, pf);
+  };
+  // V fragment (A operand of O^T) of buffer `buf`: this lane's d row
+  // `drow` = 32 dt + l31, kv columns [kvc, +16)
+  auto v_frag = [&](int buf, int drow, int kvc) BA_STEP -> frag {
+    if (VPATH == 0)
+      return ba_ld_rowslice<T, KVBLK, SWZ_V, 7>(ldsVT(buf), drow, kvc + 8 * hi);
+    return ba_ld_tr16_frag<T, D>(ldsVT(buf), lane, kvc, drow & ~31);
+  };
+  // O^T += mfma(V^T, P^T) of one subtile on prefetched V fragments.  (The
+  // LDS form is the same two loops around v_frag, written in its callers: a
+  // helper holding the loops, called last in the SUBT=1 subtile loop, moves
+  // that loop's blocks and with them the D=64 default kernels' code.)
+  auto pv_regs = [&](const frag* vv, const frag* pf) BA_STEP {
+#pragma unroll
+    for (int dt = 0; dt < D / 32; ++dt)
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+        ot[dt] = MT::mma(vv[dt * 2 + u], pf[u], ot[dt]);
+  };
+  // (row, 8-element column) of this thread's chunk c of a staged tile
+  struct chunk_rc {
+    int row, col8;
+  };
+  auto stage_rc = [&](int c) BA_STEP {
+    const int flat = tid + c * NT;
+    return chunk_rc{flat / (D / 8), flat % (D / 8)};
+  };
+#undef BA_STEP
+
+  // ---- SUBT=2/3 pipeline stage 1: the previous subtile's raw scores and
+  // its metadata, finished during the next subtile's QK cluster
+  f32x16_t stP;
+  int p_kv0 = -1;   // -1 = pipeline empty
+  int p_cur = 0;
+  bool p_full = false;
+  auto push_scores = [&](const f32x16_t& s, int kv0s, int buf, bool full) {
+    stP = s;
+    p_kv0 = kv0s;
+    p_cur = buf;
+    p_full = full;
+  };
+  auto finish_subtile = [&]() {
+    if (!p_full) mask_sub(stP, p_kv0, 0);
+    frag pf[2];
+    softmax_tail(stP, row_max2(stP), pf);
     const int kvs_l = (p_kv0 / 32) & 1;  // subtile index within its tile
 #pragma unroll
     for (int dt = 0; dt < D / 32; ++dt) {
       const int drow = dt * 32 + l31;
 #pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        frag vv = ba_ld_rowslice<T, KVBLK, SWZ_V, 7>(
-            ldsVT(p_cur), drow, kvs_l * 32 + 16 * u + 8 * hi);
-        ot[dt] = MT::mma(vv, pfp[u], ot[dt]);
-      }
+      for (int u = 0; u < 2; ++u)
+        ot[dt] = MT::mma(v_frag(p_cur, drow, kvs_l * 32 + 16 * u), pf[u],
+                         ot[dt]);
     }
   };
 
   // ---- SUBT=3 additional state: stage 2 (P fragments of subtile k-2
   // awaiting PV) and the register-prefetched K/V operands
-  static_assert(SUBT != 3 || (NBUF == 4 && VPATH == 0 && NT == 256),
-                "SUBT=3: NT=256 (1 wave/SIMD), NBUF=4, V^T image");
   frag pvf[2];                     // P fragments awaiting PV
   frag kfP[SUBT == 3 ? D / 16 : 1];  // prefetched K frags (QK of phase k)
   frag vvP[SUBT == 3 ? D / 16 : 1];  // prefetched V rowslices (PV operands)
@@ -242,7 +333,7 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
   // steady-state call sites (t >= 1: both stages provably occupied) —
   // round-3 prerequisite: the steady loop must be straight-line for the
   // hand-scheduled .s body
-  auto phase3 = [&](bool steady, int t, int kvs, int cur3, bool tile_full) {
+  auto phase3 = [&](bool steady, int t, int kvs, int cur3, bool full) {
     // --- QK(k) on the prefetched K fragments, then re-fill them for
     // the next subtile (WAR on kfP; a full phase of flight).
     // NOTE (measured): pinning this cadence with per-op
@@ -251,80 +342,30 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
     // softmax is not gap-packed.  The plain form below is the honest
     // compiler-scheduled 3-stage pipeline; the hand-placed version is
     // the round-3 full-asm body.
-    f32x16_t stQ = (f32x16_t)(0.f);
-#pragma unroll
-    for (int s = 0; s < D / 16; ++s) stQ = MT::mma(kfP[s], qf[s], stQ);
-    {
-      const int nt_t = (kvs == 0) ? t : t + 1;
-      const int nkvs = kvs ^ 1;
-      if (nt_t < nt) {
-#pragma unroll
-        for (int s = 0; s < D / 16; ++s)
-          kfP[s] = ba_ld_rowslice<T, D, SWZ_K>(ldsK(nt_t % NBUF),
-                                               nkvs * 32 + l31,
-                                               16 * s + 8 * hi);
-      }
-    }
+    const f32x16_t stQ = qk_regs(kfP);
+    load_next_kfrags(t, kvs, kfP);
     // --- softmax part 1 on stP: mask + row max (no ot/m2 writes)
     float tm = BA_NEG_BIG;
     if (steady || p_kv0 >= 0) {
-      if (!p_full) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int kv_g = p_kv0 + ba_crow(r, 0) + 4 * hi;
-          if (!(kv_g < Sk && (!causal || kv_g <= q_row))) stP[r] = BA_NEG_BIG;
-        }
-      }
-      tm = ba_max16(stP);
-      tm = fmaxf(tm, __shfl_xor(tm, 32));
-      tm *= c2;
+      if (!p_full) mask_sub(stP, p_kv0, 0);
+      tm = row_max2(stP);
     }
     // --- PV(k-2) on the prefetched operands
-    if (steady || v_kv0 >= 0) {
-#pragma unroll
-      for (int dt = 0; dt < D / 32; ++dt) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-          ot[dt] = MT::mma(vvP[dt * 2 + u], pvf[u], ot[dt]);
-      }
-    }
+    if (steady || v_kv0 >= 0) pv_regs(vvP, pvf);
     // --- softmax part 2: rescale (safe now: the PV above has landed),
     // exp2, rowsum, pack; then prefetch the new pf's V operands
     if (steady || p_kv0 >= 0) {
-      if (!__all(tm - m2 <= DEFER_THR2)) {
-        const float mnew = fmaxf(m2, tm);
-        const float alpha = ba_exp2(m2 - mnew);
-        m2 = mnew;
-        lsum *= alpha;
-#pragma unroll
-        for (int dt = 0; dt < D / 32; ++dt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) ot[dt][r] *= alpha;
-      }
-      float rowsum = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        stP[r] = ba_exp2(__builtin_fmaf(stP[r], c2, -m2));
-        rowsum += stP[r];
-      }
-      rowsum += __shfl_xor(rowsum, 32);
-      lsum += rowsum;
-      ba_build_frag_pair<T>(stP, pvf);
+      softmax_tail(stP, tm, pvf);
       v_kv0 = p_kv0;
       const int kvs_l = (p_kv0 / 32) & 1;
 #pragma unroll
-      for (int dt = 0; dt < D / 32; ++dt) {
+      for (int dt = 0; dt < D / 32; ++dt)
 #pragma unroll
         for (int u = 0; u < 2; ++u)
-          vvP[dt * 2 + u] = ba_ld_rowslice<T, KVBLK, SWZ_V, 7>(
-              ldsVT(p_cur), dt * 32 + l31, kvs_l * 32 + 16 * u + 8 * hi);
-      }
+          vvP[dt * 2 + u] = v_frag(p_cur, dt * 32 + l31, kvs_l * 32 + 16 * u);
     }
     // --- rotate stage 1
-    stP = stQ;
-    p_kv0 = t * KVBLK + kvs * 32;
-    p_cur = cur3;
-    p_full = tile_full;
+    push_scores(stQ, t * KVBLK + kvs * 32, cur3, full);
   };
 
   // staging lane offsets are loop-invariant; computing them once turns an
@@ -336,9 +377,7 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
   uint32_t k_loff[PT], v_loff[PT];
 #pragma unroll
   for (int c = 0; c < PT; ++c) {
-    const int flat = tid + c * NT;
-    const int row = flat / (D / 8);
-    const int col8 = flat % (D / 8);
+    const auto [row, col8] = stage_rc(c);
     k_loff[c] = (uint32_t)((row * k_ss + col8 * 8) * (int64_t)sizeof(T));
     v_loff[c] = (uint32_t)((row * v_ss + col8 * 8) * (int64_t)sizeof(T));
   }
@@ -361,9 +400,7 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
     }
 #pragma unroll
     for (int c = 0; c < PT; ++c) {
-      const int flat = tid + c * NT;
-      const int row = flat / (D / 8);
-      const int col8 = flat % (D / 8);
+      const auto [row, col8] = stage_rc(c);
       // clamped index instead of a guarded load: the guard compiles to
       // an exec-mask branch around every load pair (serialising the
       // staging); clamped rows re-load row Sk-1, whose values are
@@ -378,9 +415,7 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
   auto write_lds = [&](int buf, const u32x4_t* kreg, const u32x4_t* vreg) {
 #pragma unroll
     for (int c = 0; c < PT; ++c) {
-      const int flat = tid + c * NT;
-      const int row = flat / (D / 8);
-      const int col8 = flat % (D / 8);
+      const auto [row, col8] = stage_rc(c);
       if (KREG != 1) {
         const int byte = ba_swz<SWZ_K>(row * (2 * D) + col8 * 16, row);
         *(u32x4_t*)((char*)ldsK(buf) + byte) = kreg[c];
@@ -417,18 +452,9 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
       write_lds(1, kreg, vreg);
     }
     __syncthreads();
-    if (KREG == 2) {  // prime the prefetch pipeline: (tile 0, subtile 0)
-#pragma unroll
-      for (int s2 = 0; s2 < D / 16; ++s2)
-        kfr[0][s2] =
-            ba_ld_rowslice<T, D, SWZ_K>(ldsK(0), l31, 16 * s2 + 8 * hi);
-    }
-    if (SUBT == 3) {  // prime the 3-stage pipeline's K operands
-#pragma unroll
-      for (int s2 = 0; s2 < D / 16; ++s2)
-        kfP[s2] =
-            ba_ld_rowslice<T, D, SWZ_K>(ldsK(0), l31, 16 * s2 + 8 * hi);
-    }
+    // prime the prefetched K operands with (tile 0, subtile 0)
+    if (KREG == 2) load_kfrags(0, 0, kfr[0]);
+    if (SUBT == 3) load_kfrags(0, 0, kfP);
   }
   // static priority for the younger dispatch half (T5 static form):
   // wave-uniform condition via readfirstlane, one s_setprio, no flips
@@ -448,201 +474,119 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
     if (has_next) issue_loads(t + AHEAD, kreg, vreg);
 
     const bool active = !causal || (kv0 <= qb + 31);
-    if (active && SUBT == 3) {
-      const bool tile_full3 =
+    if (active) {
+      // a full tile needs no mask: inside Sk and, if causal, at or below
+      // the diagonal for every q row of this wave.  (SUBT=0 takes its own
+      // copy after its QK MFMAs: reading this one costs its register-tight
+      // tr16 kernels 4 to 8 bytes more scratch.)
+      const bool full =
           (kv0 + KVBLK <= Sk) && (!causal || (kv0 + KVBLK - 1 <= qb));
-      // NOTE: a C-level warmup peel (separate guarded/steady calls)
-      // measured -48% — four inlined phase copies bloat the loop body.
-      // The peel belongs at the .s level (round 3), where the warmup
-      // runs before the loop label.
-      [[clang::always_inline]] phase3(false, t, 0, cur, tile_full3);
-      [[clang::always_inline]] phase3(false, t, 1, cur, tile_full3);
-    } else if (active && SUBT == 2) {
-      // ---- T15 pipeline: QK(j) fills while FINISH+PV(j-1) retire
-      const bool tile_full =
-          (kv0 + KVBLK <= Sk) && (!causal || (kv0 + KVBLK - 1 <= qb));
+      if (SUBT == 3) {
+        // NOTE: a C-level warmup peel (separate guarded/steady calls)
+        // measured -48% — four inlined phase copies bloat the loop body.
+        // The peel belongs at the .s level (round 3), where the warmup
+        // runs before the loop label.
+        [[clang::always_inline]] phase3(false, t, 0, cur, full);
+        [[clang::always_inline]] phase3(false, t, 1, cur, full);
+      } else if (SUBT == 2) {
+        // ---- T15 pipeline: QK(j) fills while FINISH+PV(j-1) retire
 #pragma unroll
-      for (int kvs = 0; kvs < 2; ++kvs) {
-        f32x16_t stQ = (f32x16_t)(0.f);
-#pragma unroll
-        for (int s2 = 0; s2 < D / 16; ++s2) {
-          frag kf = ba_ld_rowslice<T, D, SWZ_K>(ldsK(cur), kvs * 32 + l31,
-                                                16 * s2 + 8 * hi);
-          stQ = MT::mma(kf, qf[s2], stQ);
+        for (int kvs = 0; kvs < 2; ++kvs) {
+          const f32x16_t stQ = qk_lds(cur, kvs);
+          if (p_kv0 >= 0) [[clang::always_inline]] finish_subtile();
+          push_scores(stQ, kv0 + kvs * 32, cur, full);
         }
-        if (p_kv0 >= 0) [[clang::always_inline]] finish_subtile();
-        stP = stQ;
-        p_kv0 = kv0 + kvs * 32;
-        p_cur = cur;
-        p_full = tile_full;
-      }
-    } else if (active && SUBT == 1) {
-      // ---- per-subtile pipeline: {QK, softmax, PV} x 2, independent
-      // chains so the scheduler overlaps PV(0) with QK(1)
-      const bool tile_full =
-          (kv0 + KVBLK <= Sk) && (!causal || (kv0 + KVBLK - 1 <= qb));
-      constexpr float DEFER_THR = 8.f;
+      } else if (SUBT == 1) {
+        // ---- per-subtile pipeline: {QK, softmax, PV} x 2, independent
+        // chains so the scheduler overlaps PV(0) with QK(1)
 #pragma unroll
-      for (int kvs = 0; kvs < 2; ++kvs) {
-        f32x16_t st = (f32x16_t)(0.f);
+        for (int kvs = 0; kvs < 2; ++kvs) {
+          frag* kres = kfr[KREG == 1 ? kvs : 0];
+          f32x16_t st = KREG ? qk_regs(kres) : qk_lds(cur, kvs);
+          // KREG=1: this subtile's K block is consumed — re-issue its
+          // global loads for the next tile at once (WAR on the same
+          // registers; HBM latency hides under softmax + PV + staging)
+          if (KREG == 1 && has_next) load_k_sub(t + AHEAD, kvs, kres);
+          // KREG=2: re-fill the fragment set from LDS one subtile ahead
+          // (tile t+1's buffer was staged two tiles ago, ordered by the
+          // per-tile barrier)
+          if (KREG == 2) load_next_kfrags(t, kvs, kres);
+          if (!full) mask_sub(st, kv0, kvs * 32);
+          frag pf[2];
+          softmax_tail(st, row_max2(st), pf);
 #pragma unroll
-        for (int s2 = 0; s2 < D / 16; ++s2) {
-          frag kf = KREG ? kfr[KREG == 1 ? kvs : 0][s2]
-                         : ba_ld_rowslice<T, D, SWZ_K>(
-                               ldsK(cur), kvs * 32 + l31, 16 * s2 + 8 * hi);
-          st = MT::mma(kf, qf[s2], st);
-        }
-        // KREG=1: this subtile's K block is consumed — re-issue its
-        // global loads for the next tile at once (WAR on the same
-        // registers; HBM latency hides under softmax + PV + staging)
-        if (KREG == 1 && has_next)
-          load_k_sub(t + AHEAD, kvs, kfr[KREG == 1 ? kvs : 0]);
-        // KREG=2: re-fill the fragment set from LDS one subtile ahead
-        // ((t,0)->(t,1)->(t+1,0); tile t+1's buffer was staged two
-        // tiles ago, ordered by the per-tile barrier)
-        if (KREG == 2) {
-          const int pn_t = (kvs == 0) ? t : t + 1;
-          if (pn_t < nt) {
-            const int pkvs = kvs ^ 1;
+          for (int dt = 0; dt < D / 32; ++dt) {
+            const int drow = dt * 32 + l31;
 #pragma unroll
-            for (int s2 = 0; s2 < D / 16; ++s2)
-              kfr[0][s2] = ba_ld_rowslice<T, D, SWZ_K>(
-                  ldsK(pn_t % NBUF), pkvs * 32 + l31, 16 * s2 + 8 * hi);
+            for (int u = 0; u < 2; ++u)
+              ot[dt] = MT::mma(v_frag(cur, drow, kvs * 32 + 16 * u), pf[u],
+                               ot[dt]);
           }
         }
-        // fold the softmax scale into the exp argument (exp2+fma): the
-        // row max is taken on RAW scores (max commutes with c2 > 0), the
-        // scale costs one multiply on the max instead of 16 per subtile
-        if (!tile_full) {
+      } else {
+        // ---- SUBT=0: joint softmax over both subtiles, on scores
+        // pre-scaled into the exp2 domain (+ mask only on boundary tiles);
+        // the two QK chains interleave per K fragment
+        f32x16_t st[2] = {(f32x16_t)(0.f), (f32x16_t)(0.f)};
+#pragma unroll
+        for (int s = 0; s < D / 16; ++s) {
+          frag k0 = ba_ld_rowslice<T, D, SWZ_K>(ldsK(cur), l31, 16 * s + 8 * hi);
+          frag k1 =
+              ba_ld_rowslice<T, D, SWZ_K>(ldsK(cur), 32 + l31, 16 * s + 8 * hi);
+          st[0] = MT::mma(k0, qf[s], st[0]);
+          st[1] = MT::mma(k1, qf[s], st[1]);
+        }
+        const bool full0 =
+            (kv0 + KVBLK <= Sk) && (!causal || (kv0 + KVBLK - 1 <= qb));
+        if (full0) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int kv_g = kv0 + kvs * 32 + ba_crow(r, 0) + 4 * hi;
-            if (!(kv_g < Sk && (!causal || kv_g <= q_row))) st[r] = BA_NEG_BIG;
+            st[0][r] *= c2;
+            st[1][r] *= c2;
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int kv_g0 = kv0 + ba_crow(r, 0) + 4 * hi;
+            const int kv_g1 = kv_g0 + 32;
+            st[0][r] = (kv_g0 < Sk && (!causal || kv_g0 <= q_row))
+                           ? st[0][r] * c2
+                           : BA_NEG_BIG;
+            st[1][r] = (kv_g1 < Sk && (!causal || kv_g1 <= q_row))
+                           ? st[1][r] * c2
+                           : BA_NEG_BIG;
           }
         }
-        float tm = ba_max16(st);
+        float tm = BA_NEG_BIG;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tm = fmaxf(tm, fmaxf(st[0][r], st[1][r]));
         tm = fmaxf(tm, __shfl_xor(tm, 32));
-        tm *= c2;  // into the exp2 domain
-        if (!__all(tm - m2 <= DEFER_THR)) {
-          const float mnew = fmaxf(m2, tm);
-          const float alpha = ba_exp2(m2 - mnew);
-          m2 = mnew;
-          lsum *= alpha;
-#pragma unroll
-          for (int dt = 0; dt < D / 32; ++dt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) ot[dt][r] *= alpha;
-        }
+        rescale(tm);
         float rowsum = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          st[r] = ba_exp2(__builtin_fmaf(st[r], c2, -m2));
-          rowsum += st[r];
+          st[0][r] = ba_exp2(st[0][r] - m2);
+          st[1][r] = ba_exp2(st[1][r] - m2);
+          rowsum += st[0][r] + st[1][r];
         }
         rowsum += __shfl_xor(rowsum, 32);
         lsum += rowsum;
-        frag pf[2];
-        ba_build_frag_pair<T>(st, pf);
+
+        // ---- P -> fragments, O^T += mfma(V^T, P^T); the two subtiles
+        // alternate per u (the accumulation order of this form)
+        frag pf[2][2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) ba_build_frag_pair<T>(st[j], pf[j]);
 #pragma unroll
         for (int dt = 0; dt < D / 32; ++dt) {
           const int drow = dt * 32 + l31;
 #pragma unroll
           for (int u = 0; u < 2; ++u) {
-            frag vv;
-            if (VPATH == 0)
-              vv = ba_ld_rowslice<T, KVBLK, SWZ_V, 7>(ldsVT(cur), drow,
-                                                      kvs * 32 + 16 * u + 8 * hi);
-            else
-              vv = ba_ld_tr16_frag<T, D>(ldsVT(cur), lane,
-                                         kvs * 32 + 16 * u, dt * 32);
-            ot[dt] = MT::mma(vv, pf[u], ot[dt]);
+            const frag v0 = v_frag(cur, drow, 16 * u);
+            const frag v1 = v_frag(cur, drow, 32 + 16 * u);
+            ot[dt] = MT::mma(v0, pf[0][u], ot[dt]);
+            ot[dt] = MT::mma(v1, pf[1][u], ot[dt]);
           }
-        }
-      }
-    } else if (active) {
-
-      // ---- S^T = mfma(K, Q): two 32-kv subtiles
-      f32x16_t st0 = (f32x16_t)(0.f), st1 = (f32x16_t)(0.f);
-#pragma unroll
-      for (int s = 0; s < D / 16; ++s) {
-        frag k0 = ba_ld_rowslice<T, D, SWZ_K>(ldsK(cur), l31, 16 * s + 8 * hi);
-        frag k1 =
-            ba_ld_rowslice<T, D, SWZ_K>(ldsK(cur), 32 + l31, 16 * s + 8 * hi);
-        st0 = MT::mma(k0, qf[s], st0);
-        st1 = MT::mma(k1, qf[s], st1);
-      }
-      // ---- scale into exp2 domain (+ mask only on boundary tiles)
-      const bool tile_full =
-          (kv0 + KVBLK <= Sk) && (!causal || (kv0 + KVBLK - 1 <= qb));
-      if (tile_full) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          st0[r] *= c2;
-          st1[r] *= c2;
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int kv_g0 = kv0 + ba_crow(r, 0) + 4 * hi;
-          const int kv_g1 = kv_g0 + 32;
-          st0[r] = (kv_g0 < Sk && (!causal || kv_g0 <= q_row)) ? st0[r] * c2
-                                                               : BA_NEG_BIG;
-          st1[r] = (kv_g1 < Sk && (!causal || kv_g1 <= q_row)) ? st1[r] * c2
-                                                               : BA_NEG_BIG;
-        }
-      }
-      // ---- online softmax update (lane-local), defer-max (T13):
-      // skip the O/l rescale while the running max grows by <= THR
-      // (exp2 domain); P is then bounded by 2^THR instead of 1, which
-      // the fp32 accumulate absorbs.  Decision taken BEFORE this tile's
-      // P is exponentiated (the textbook-safe order); wave-uniform.
-      constexpr float DEFER_THR = 8.f;
-      float tm = BA_NEG_BIG;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) tm = fmaxf(tm, fmaxf(st0[r], st1[r]));
-      tm = fmaxf(tm, __shfl_xor(tm, 32));
-      const bool rescale = !__all(tm - m2 <= DEFER_THR);
-      if (rescale) {
-        const float mnew = fmaxf(m2, tm);
-        const float alpha = ba_exp2(m2 - mnew);
-        m2 = mnew;
-        lsum *= alpha;
-#pragma unroll
-        for (int dt = 0; dt < D / 32; ++dt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) ot[dt][r] *= alpha;
-      }
-      float rowsum = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        st0[r] = ba_exp2(st0[r] - m2);
-        st1[r] = ba_exp2(st1[r] - m2);
-        rowsum += st0[r] + st1[r];
-      }
-      rowsum += __shfl_xor(rowsum, 32);
-      lsum += rowsum;
-
-      // ---- P -> fragments, O^T += mfma(V^T, P^T)
-      frag pf0[2], pf1[2];
-      ba_build_frag_pair<T>(st0, pf0);
-      ba_build_frag_pair<T>(st1, pf1);
-#pragma unroll
-      for (int dt = 0; dt < D / 32; ++dt) {
-        const int drow = dt * 32 + l31;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          frag v0, v1;
-          if (VPATH == 0) {
-            v0 = ba_ld_rowslice<T, KVBLK, SWZ_V, 7>(ldsVT(cur), drow,
-                                                    16 * u + 8 * hi);
-            v1 = ba_ld_rowslice<T, KVBLK, SWZ_V, 7>(ldsVT(cur), drow,
-                                                    32 + 16 * u + 8 * hi);
-          } else {
-            v0 = ba_ld_tr16_frag<T, D>(ldsVT(cur), lane, 16 * u, dt * 32);
-            v1 = ba_ld_tr16_frag<T, D>(ldsVT(cur), lane, 32 + 16 * u, dt * 32);
-          }
-          ot[dt] = MT::mma(v0, pf0[u], ot[dt]);
-          ot[dt] = MT::mma(v1, pf1[u], ot[dt]);
         }
       }
     }
@@ -688,13 +632,7 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
   }
   if (SUBT == 2 && p_kv0 >= 0) finish_subtile();  // drain the pipeline
   if (SUBT == 3) {  // drain both pending stages (PV first: scale order)
-    if (v_kv0 >= 0) {
-#pragma unroll
-      for (int dt = 0; dt < D / 32; ++dt)
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-          ot[dt] = MT::mma(vvP[dt * 2 + u], pvf[u], ot[dt]);
-    }
+    if (v_kv0 >= 0) pv_regs(vvP, pvf);
     if (p_kv0 >= 0) finish_subtile();
   }
 
@@ -750,50 +688,6 @@ __global__ void attn_fwd_finalize_kernel(
   if (sub == 0)
     lse[((int64_t)b * N + n) * S + s] =
         BA_LN2 * (m[((int64_t)b * N + n) * S + s] + log2f(lv));
-}
-
-// ---- MFMA layout probe (test support): D = A*B for one 32x32x16 tile,
-// with A,B,D moved per the layout assumptions above.  a: [32][16] row-major,
-// b: [16][32] row-major, d: [32][32] row-major, all dense in HBM.
-template <typename T>
-__global__ void mfma_probe_kernel(const T* a, const T* b, float* d) {
-  using MT = mfma_traits<T>;
-  using frag = typename MT::frag;
-  const int lane = threadIdx.x & 63;
-  const int l31 = lane & 31, hi = lane >> 5;
-  frag af, bf;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    af[j] = a[l31 * 16 + 8 * hi + j];    // A[row=l31][k=8*hi+j]
-    bf[j] = b[(8 * hi + j) * 32 + l31];  // B[k=8*hi+j][col=l31]
-  }
-  f32x16_t c = (f32x16_t)(0.f);
-  c = MT::mma(af, bf, c);
-#pragma unroll
-  for (int r = 0; r < 16; ++r) d[ba_crow(r, hi) * 32 + l31] = c[r];
-}
-
-// ---- ds_read_tr16_b64 semantics probe (test/dev support).
-// Fills LDS with element-index pattern, issues the transpose-read with a
-// per-mode address pattern, dumps each lane's 4 returned u16s.
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-__global__ void tr16_probe_kernel(int mode, int* out) {
-  __shared__ unsigned short lds[4096];
-  for (int i = threadIdx.x; i < 4096; i += 64) lds[i] = (unsigned short)i;
-  __syncthreads();
-  const int l = threadIdx.x & 63;
-  int e;
-  switch (mode) {
-    case 0: e = 0; break;               // uniform base
-    case 1: e = (l & 15) * 4; break;    // per-16-group column stride 4
-    case 2: e = l * 4; break;           // per-lane stride 4
-    case 3: e = (l >> 4) * 64; break;   // per-quarter base
-    default: e = (l & 15) * 4 + (l >> 4) * 256; break;
-  }
-  auto p = (__attribute__((address_space(3))) s16x4_t*)&lds[e];
-  s16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(p);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) out[l * 4 + j] = (int)(unsigned short)v[j];
 }
 
 }  // namespace
@@ -992,20 +886,4 @@ extern "C" int bahip_attn_fwd_finalize(const float* acc, const float* m,
                                                 (int)N);
     return ba_launch_status();
   });
-}
-
-extern "C" int bahip_tr16_probe(int mode, int* out, void* stream) {
-  tr16_probe_kernel<<<1, 64, 0, (hipStream_t)stream>>>(mode, out);
-  return ba_launch_status();
-}
-
-extern "C" int bahip_mfma_probe(const void* a, const void* b, float* d,
-                                int dtype, void* stream) {
-  if (dtype == BAHIP_BF16)
-    mfma_probe_kernel<__bf16><<<1, 64, 0, (hipStream_t)stream>>>(
-        (const __bf16*)a, (const __bf16*)b, d);
-  else
-    mfma_probe_kernel<_Float16><<<1, 64, 0, (hipStream_t)stream>>>(
-        (const _Float16*)a, (const _Float16*)b, d);
-  return ba_launch_status();
 }

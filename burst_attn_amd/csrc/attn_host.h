@@ -1,6 +1,6 @@
-// Host-side helpers shared by the C-ABI entry points in attn_fwd.hip and
-// attn_bwd.hip: the last-error message, env knobs, launch status, and the
-// (head_dim, dtype) -> <T, D> dispatch.
+// Host-side helpers shared by the C-ABI entry points in attn_fwd.hip,
+// attn_bwd.hip and probes.hip: the last-error message, env knobs, launch
+// status, and the (head_dim, dtype) -> <T, D> dispatch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>

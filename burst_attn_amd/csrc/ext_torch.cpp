@@ -9,9 +9,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "../../include/burst_attn_hip.h"
-
-extern "C" int bahip_mfma_probe(const void*, const void*, float*, int, void*);
-extern "C" int bahip_tr16_probe(int, int*, void*);
+#include "probes.h"
 
 namespace {
 

@@ -689,3 +689,48 @@ def test_fwd_alt_paths_carry_in_vs_default(knobs, dtype, monkeypatch):
     o_alt, lse_alt = _carry_in_two_halves(q, k, v, scale, dtype)
     torch.testing.assert_close(o_alt.float(), o_ref.float(), **TOL[dtype])
     torch.testing.assert_close(lse_alt, lse_ref, rtol=1e-3, atol=2e-2)
+
+
+def _d64_both_forms(q, ka, va, kb, vb, scale, causal, dtype):
+    """The stateless tile on (ka, va), and the two-call carry-in form: a
+    fresh accumulator on (ka, va) under the mask, then (kb, vb) unmasked
+    merged in-kernel and finalized, the way a ring's diagonal round is
+    followed by a full one."""
+    ext = _ext()
+    o, lse = ext.attn_fwd(q, ka, va, scale, causal)
+    b, sq, n, d = q.shape
+    acc = torch.empty(b, sq, n, d, dtype=torch.float32, device=q.device)
+    m = torch.empty(b, n, sq, dtype=torch.float32, device=q.device)
+    l = torch.empty(b, n, sq, dtype=torch.float32, device=q.device)
+    ext.attn_fwd_accum(q, ka, va, scale, causal, acc, m, l, False)
+    ext.attn_fwd_accum(q, kb, vb, scale, False, acc, m, l, True)
+    o_c, lse_c = ext.attn_fwd_finalize(acc, m, l, dtype)
+    return o, lse, o_c, lse_c
+
+
+_D64_DEFAULT = {}
+
+
+@FWD_ALT_KNOBS
+@pytest.mark.parametrize("causal", [False, True])
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+def test_fwd_alt_paths_d64_vs_default(knobs, causal, dtype, monkeypatch):
+    """The knob sets at head_dim 64 (the tests above run them at 128 only),
+    stateless and carry-in, against the default variant.  Sq = Sk = 296:
+    five kv tiles, so NBUF=4 wraps; the last one a ragged 40 rows; a ragged
+    q tail for both NT=512 and NT=256; N=4 over Nk=2 keeps the grouped-query
+    head mapping live."""
+    scale = 1.0 / math.sqrt(64)
+    if (dtype, causal) not in _D64_DEFAULT:
+        q = _rand(1, 296, 4, 64, dtype, 150)
+        kv = [_rand(1, 296, 2, 64, dtype, 151 + i) for i in range(4)]
+        _D64_DEFAULT[dtype, causal] = (
+            q, kv, _d64_both_forms(q, *kv, scale, causal, dtype))
+    q, kv, ref = _D64_DEFAULT[dtype, causal]
+    for key, val in knobs.items():
+        monkeypatch.setenv(key, val)
+    alt = _d64_both_forms(q, *kv, scale, causal, dtype)
+    for (o_alt, lse_alt), (o_ref, lse_ref) in ((alt[:2], ref[:2]),
+                                               (alt[2:], ref[2:])):
+        torch.testing.assert_close(o_alt.float(), o_ref.float(), **TOL[dtype])
+        torch.testing.assert_close(lse_alt, lse_ref, rtol=1e-3, atol=2e-2)
