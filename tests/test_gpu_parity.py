@@ -27,6 +27,7 @@ BWD_TOL = {
     torch.float16: dict(rtol=5e-3, atol=2e-2),
     torch.bfloat16: dict(rtol=3e-2, atol=1e-1),
 }
+LSE_TOL = dict(rtol=1e-3, atol=2e-2)
 
 
 def _ext():
@@ -74,7 +75,7 @@ def test_fwd_tile_parity(b, sq, sk, n, d, causal, dtype):
     o, lse = _ext().attn_fwd(q, k, v, scale, causal)
     o_ref, lse_ref = oracle.tile_fwd(q.cpu(), k.cpu(), v.cpu(), scale, causal)
     torch.testing.assert_close(o.cpu(), o_ref, **TOL[dtype])
-    torch.testing.assert_close(lse.cpu(), lse_ref, rtol=1e-3, atol=2e-2)
+    torch.testing.assert_close(lse.cpu(), lse_ref, **LSE_TOL)
 
 
 @pytest.mark.parametrize("dtype", [torch.float16])
@@ -221,7 +222,7 @@ def test_fwd_defer_max_rescale_forced(dtype):
     o, lse = _ext().attn_fwd(qg, kg, vg, scale, False)
     o_ref, lse_ref = oracle.tile_fwd(qg.cpu(), kg.cpu(), vg.cpu(), scale, False)
     torch.testing.assert_close(o.cpu(), o_ref, **TOL[dtype])
-    torch.testing.assert_close(lse.cpu(), lse_ref, rtol=1e-3, atol=2e-2)
+    torch.testing.assert_close(lse.cpu(), lse_ref, **LSE_TOL)
     # causal flavour too (different masking interaction)
     o2, _ = _ext().attn_fwd(qg, kg, vg, scale, True)
     o2_ref, _ = oracle.tile_fwd(qg.cpu(), kg.cpu(), vg.cpu(), scale, True)
@@ -246,7 +247,7 @@ def test_accum_carry_in_matches_stateless(dtype):
     o, lse = P.fwd_finalize(st, dtype)
     o_full, lse_full = _ext().attn_fwd(q, k, v, scale, False)
     torch.testing.assert_close(o.float(), o_full, **TOL[dtype])
-    torch.testing.assert_close(lse, lse_full, rtol=1e-3, atol=2e-2)
+    torch.testing.assert_close(lse, lse_full, **LSE_TOL)
     # row-offset window: extra kv merged only into rows [half:]
     half = s // 2
     st2 = P.fwd_accum(None, q, k[:, :s], v[:, :s], scale, False)
@@ -498,9 +499,10 @@ def test_fwd_shape_fuzz():
         scale = 1.0 / math.sqrt(d)
         o, lse = ext.attn_fwd(q, k, v, scale, causal)
         o_ref, lse_ref = oracle.tile_fwd(q.cpu(), k.cpu(), v.cpu(), scale, causal)
+        case = f"case {i}: b={b} sq={sq} sk={sk} n={n} d={d} causal={causal}"
         torch.testing.assert_close(
-            o.cpu(), o_ref, **TOL[dtype]
-        ), f"case {i}: b={b} sq={sq} sk={sk} n={n} d={d} causal={causal}"
+            o.cpu(), o_ref, msg=lambda m: f"{case}\n{m}", **TOL[dtype]
+        )
 
 
 def test_error_paths(monkeypatch):
@@ -565,7 +567,7 @@ def test_large_size_direct_parity():
     o_ref, lse_ref = oracle.tile_fwd(q.cpu(), k.cpu(), v.cpu(), scale, True,
                                      q_block=1024, k_block=1024)
     torch.testing.assert_close(o.cpu(), o_ref, **TOL[dtype])
-    torch.testing.assert_close(lse.cpu(), lse_ref, rtol=1e-3, atol=2e-2)
+    torch.testing.assert_close(lse.cpu(), lse_ref, **LSE_TOL)
     dq_r, dk_r, dv_r = oracle.tile_bwd(do.cpu(), q.cpu(), k.cpu(), v.cpu(),
                                        lse_ref, scale, True, o=o_ref,
                                        q_block=1024, k_block=1024)
@@ -603,7 +605,7 @@ def test_asm_module_fwd_parity(asm, dtype, monkeypatch):
             o_a, lse_a = pa.fwd_finalize(st_a, dtype)
             o_b, lse_b = base.fwd_finalize(st_b, dtype)
             torch.testing.assert_close(o_a.float(), o_b.float(), **TOL[dtype])
-            torch.testing.assert_close(lse_a, lse_b, rtol=1e-3, atol=2e-2)
+            torch.testing.assert_close(lse_a, lse_b, **LSE_TOL)
     # D=64 falls back to the in-binary kernel rather than failing
     q = _rand(1, 256, 2, 64, dtype, 80)
     k = _rand(1, 256, 2, 64, dtype, 81)
@@ -649,7 +651,7 @@ def test_fwd_alt_paths_vs_default(knobs, causal, dtype, monkeypatch):
         for key in knobs:
             monkeypatch.delenv(key)
         torch.testing.assert_close(o_alt, o_ref, **TOL[dtype])
-        torch.testing.assert_close(lse_alt, lse_ref, rtol=1e-3, atol=2e-2)
+        torch.testing.assert_close(lse_alt, lse_ref, **LSE_TOL)
 
 
 def _carry_in_two_halves(q, k, v, scale, dtype):
@@ -688,7 +690,7 @@ def test_fwd_alt_paths_carry_in_vs_default(knobs, dtype, monkeypatch):
         monkeypatch.setenv(key, val)
     o_alt, lse_alt = _carry_in_two_halves(q, k, v, scale, dtype)
     torch.testing.assert_close(o_alt.float(), o_ref.float(), **TOL[dtype])
-    torch.testing.assert_close(lse_alt, lse_ref, rtol=1e-3, atol=2e-2)
+    torch.testing.assert_close(lse_alt, lse_ref, **LSE_TOL)
 
 
 def _d64_both_forms(q, ka, va, kb, vb, scale, causal, dtype):
@@ -733,4 +735,4 @@ def test_fwd_alt_paths_d64_vs_default(knobs, causal, dtype, monkeypatch):
     for (o_alt, lse_alt), (o_ref, lse_ref) in ((alt[:2], ref[:2]),
                                                (alt[2:], ref[2:])):
         torch.testing.assert_close(o_alt.float(), o_ref.float(), **TOL[dtype])
-        torch.testing.assert_close(lse_alt, lse_ref, rtol=1e-3, atol=2e-2)
+        torch.testing.assert_close(lse_alt, lse_ref, **LSE_TOL)
