@@ -119,12 +119,15 @@ def _build_asm_hsaco(verbose, force):
           f"-mcpu={ARCH}", "-c", s_path, "-o", o_path], verbose)
     _run([lld, "-shared", o_path, "-o", hsaco], verbose)
     # record the mangled names of the dispatchable variants (the SUBT=1
-    # NBUF=2 production instantiations, accum form, fp16 and bf16)
+    # NBUF=2 production instantiations, accum form, fp16 and bf16).  The
+    # last argument is VSRC=0: the module path launches the kernel that
+    # transposes V itself, with today's fwd_args (the VSRC=1 twin reads the
+    # V^T image and differs only in that last Li1E).
     text = open(s_path).read()
     names = {}
     for key, pat in (
-        ("f16_accum", r"_ZN12_GLOBAL__N_115attn_fwd_kernelIDF16_Li128ELi64ELi1ELi0ELi1ELi512ELi2ELi0E\S*"),
-        ("bf16_accum", r"_ZN12_GLOBAL__N_115attn_fwd_kernelIDF16bLi128ELi64ELi1ELi0ELi1ELi512ELi2ELi0E\S*"),
+        ("f16_accum", r"_ZN12_GLOBAL__N_115attn_fwd_kernelIDF16_Li128ELi64ELi1ELi0ELi1ELi512ELi2ELi0ELi0EE\S*"),
+        ("bf16_accum", r"_ZN12_GLOBAL__N_115attn_fwd_kernelIDF16bLi128ELi64ELi1ELi0ELi1ELi512ELi2ELi0ELi0EE\S*"),
     ):
         m = re.search(r"\.globl\t(" + pat + ")", text)
         if m:

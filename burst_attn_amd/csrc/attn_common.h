@@ -8,14 +8,21 @@
 //    output normaliser) is LANE-LOCAL: the 32x32 MFMA D-layout gives each
 //    lane one output COLUMN (col = lane&31), so with q on the column axis
 //    the whole online-softmax state lives in registers of the lane that
-//    owns that q row.  No cross-lane traffic per tile except one
-//    shfl_xor(32) for the max/sum halves.
+//    owns that q row.  No cross-lane traffic per tile except the exchange
+//    of the max/sum lane halves: shfl_xor(32), or ba_half_pair (one
+//    v_permlane32_swap, no LDS) in the forward's image-form kernels.
 //  * P (f32, D-layout) is converted to MFMA A/B fragments in-register via
 //    pack-to-2xT + v_permlane32_swap (lane halves exchange) — no LDS
 //    round trip for P.
 //  * K (and V) tiles are staged in LDS with a 16-byte XOR swizzle
 //    (byte ^= (row & SWZ) << 4) so the per-lane row-slice ds_read_b128 of
 //    the MFMA fragments is bank-conflict-free.
+//  * The forward's V lives in LDS TRANSPOSED ([D][kv], so PV fragments are
+//    row slices too).  Who transposes is a choice (VSRC in attn_fwd.hip):
+//    the forward kernel itself at staging time (ba_st_transposed, 8 two-byte
+//    LDS writes per 16-byte chunk, repeated by every workgroup that visits
+//    the tile), or a pre-pass that writes the V^T image of vt_image.h to HBM
+//    once per call, after which staging a V tile is 16-byte copies like K's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -107,6 +114,18 @@ __device__ __forceinline__ void ba_build_frag_pair(
                  (unsigned int)r0[1], (unsigned int)r1[1]};
     out[u] = __builtin_bit_cast(typename mfma_traits<T>::frag, w);
   }
+}
+
+// Both lane halves' values of x (lanes l and l ^ 32) in every lane, through
+// one v_permlane32_swap with x in both operands: no LDS round trip, unlike
+// __shfl_xor(x, 32) (ds_bpermute_b32 + s_waitcnt lgkmcnt(0)).  max and a
+// two-term add commute, so fmaxf(lo, hi) and lo + hi are bitwise what
+// fmaxf(x, other) and x + other give.
+__device__ __forceinline__ void ba_half_pair(float x, float& lo, float& hi) {
+  const int xi = __builtin_bit_cast(int, x);
+  const i32x2_t r = __builtin_amdgcn_permlane32_swap(xi, xi, false, false);
+  lo = __builtin_bit_cast(float, (int)r[0]);
+  hi = __builtin_bit_cast(float, (int)r[1]);
 }
 
 // 16-value max via 3-input nesting (clang fuses fmaxf chains to v_max3)

@@ -14,7 +14,10 @@
 //     (XOR-swizzled); V is stored TRANSPOSED [D][kv] at staging time so
 //     that both operands' MFMA fragments are plain 16B row-slice
 //     ds_read_b128s — no per-element transposed gathers (those made the
-//     compiler hoist & spill hundreds of swizzled addresses).
+//     compiler hoist & spill hundreds of swizzled addresses).  With a
+//     workspace the transpose is done once per call by
+//     attn_vt_image_kernel instead and the default variant's VSRC=1 form
+//     copies V^T tiles as it copies K (vt_image.h).
 //   * per kv tile and wave: S^T = mfma(K, Q) (2 x D/16 MFMAs),
 //     online-softmax update (lane-local m/l in exp2 domain),
 //     P->fragments in-register (pack + permlane32_swap),
@@ -25,6 +28,7 @@
 #include "attn_host.h"
 #include "fwd_variants.h"
 #include "gqa_heads.h"
+#include "vt_image.h"
 
 #include <stddef.h>
 
@@ -87,8 +91,14 @@ __device__ __forceinline__ int ba_buf_of(ba_dyn d) { return d.value; }
 // t+1's buffer two tiles ago and a barrier every tile orders it.  The
 // QK cluster's lgkm park (SQ_WAIT_ANY 38% in the r2 PMC taxonomy)
 // becomes overlap.  Requires SUBT=1, NBUF=4, VPATH=0.
+// VSRC: where the V^T LDS image comes from.  0 = V itself, transposed at
+// staging time (16 two-byte LDS writes per thread and tile at D=128);
+// 1 = the V^T image of vt_image.h, written once per call by
+// attn_vt_image_kernel: `v` points at the image, v_sb / v_sh are its batch
+// and head strides, v_ss is unused, and a tile's staging is PT 16-byte
+// copies like K's.  Default variant <0,1,512,2,0> only.
 template <typename T, int D, int KVBLK, int OUT_STATE, int VPATH, int SUBT,
-          int NT = 512, int NBUF = 2, int KREG = 0>
+          int NT = 512, int NBUF = 2, int KREG = 0, int VSRC = 0>
 __global__ __launch_bounds__(NT) void attn_fwd_kernel(
     const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
     float* __restrict__ o, float* __restrict__ lse,
@@ -108,12 +118,22 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
   constexpr int SWZ_V = 7;                    // V^T image rows are 128 bytes
   constexpr int PT = (KVBLK * D / 8) / NT;
   constexpr int QROWS = NT / 2;  // q rows per workgroup (32 per wave)
+  // The image-form kernels combine the lane halves of the row max and the
+  // row sum with ba_half_pair (v_permlane32_swap) instead of __shfl_xor
+  // (ds_bpermute_b32 + s_waitcnt lgkmcnt(0), which drains the V fragment
+  // reads in flight): same bits, measured +0.9 % on top of the image
+  // (profiles/fwd_vt/README.md).  The VSRC=0 kernels keep __shfl_xor, so
+  // their code is the code the tuned numbers and the module path refer to.
+  constexpr bool HSWAP = VSRC == 1;
   static_assert(PT >= 1, "tile must fill at least one chunk per thread");
 
   static_assert(KREG != 1 || (SUBT == 1 && NBUF == 2 && VPATH == 0),
                 "KREG=1 path: SUBT=1, NBUF=2, V^T image only");
   static_assert(KREG != 2 || (SUBT == 1 && NBUF == 4 && VPATH == 0),
                 "KREG=2 path: SUBT=1, NBUF=4 (cross-barrier prefetch)");
+  static_assert(VSRC == 0 || (VPATH == 0 && SUBT == 1 && KREG == 0 &&
+                              KVBLK == BA_VT_KVBLK),
+                "the V^T image source: b128-read V^T LDS image, SUBT=1");
   // single LDS object: [NBUF buffers][K row-major | V transposed][KVBLK*D]
   // (KREG=1: V transposed only)
   constexpr int IMGS_F = (KREG == 1) ? 1 : 2;
@@ -227,7 +247,13 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
   // subtile
   auto row_max2 = [&](const f32x16_t& s) BA_STEP {
     float tm = ba_max16(s);
-    tm = fmaxf(tm, __shfl_xor(tm, 32));
+    if (HSWAP) {
+      float lo, hi2;
+      ba_half_pair(tm, lo, hi2);
+      tm = fmaxf(lo, hi2);
+    } else {
+      tm = fmaxf(tm, __shfl_xor(tm, 32));
+    }
     return tm * c2;
   };
   // online-softmax rescale (lane-local), defer-max (T13): skip the O/l
@@ -258,7 +284,13 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
       s[r] = ba_exp2(__builtin_fmaf(s[r], c2, -m2));
       rowsum += s[r];
     }
-    rowsum += __shfl_xor(rowsum, 32);
+    if (HSWAP) {
+      float lo, hi2;
+      ba_half_pair(rowsum, lo, hi2);
+      rowsum = lo + hi2;
+    } else {
+      rowsum += __shfl_xor(rowsum, 32);
+    }
     lsum += rowsum;
     ba_build_frag_pair<T>(s, pf);
   };
@@ -383,9 +415,19 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
   }
   const bool stage_lin =
       (int64_t)(KVBLK - 1) * k_ss * (int64_t)sizeof(T) + 16 <= 0xffffffffLL &&
-      (int64_t)(KVBLK - 1) * v_ss * (int64_t)sizeof(T) + 16 <= 0xffffffffLL;
+      (VSRC == 1 ||
+       (int64_t)(KVBLK - 1) * v_ss * (int64_t)sizeof(T) + 16 <= 0xffffffffLL);
   auto issue_loads = [&](int tile, u32x4_t* kreg, u32x4_t* vreg) {
     const int kv0 = tile * KVBLK;
+    // image source: chunk c of the tile's block, a scalar block base plus
+    // the lane's invariant offset.  The last block is zero-padded to 64
+    // columns, so no tile needs a clamp.
+    if (VSRC == 1) {
+      const char* vb = (const char*)(vp + tile * ba_vt_block_elems(D));
+#pragma unroll
+      for (int c = 0; c < PT; ++c)
+        vreg[c] = *(const u32x4_t*)(vb + (uint32_t)((tid + c * NT) * 16));
+    }
     // the fast path's invariant offsets cost live registers the SUBT=2/3
     // pipelined variants cannot spare (they spill); production SUBT=1 only
     if (SUBT == 1 && stage_lin && kv0 + KVBLK <= Sk) {
@@ -394,7 +436,7 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
 #pragma unroll
       for (int c = 0; c < PT; ++c) {
         if (KREG != 1) kreg[c] = *(const u32x4_t*)(kb + k_loff[c]);
-        vreg[c] = *(const u32x4_t*)(vb + v_loff[c]);
+        if (VSRC == 0) vreg[c] = *(const u32x4_t*)(vb + v_loff[c]);
       }
       return;
     }
@@ -409,7 +451,8 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
       const int kvc = kvg < Sk ? kvg : (Sk - 1);
       if (KREG != 1)
         kreg[c] = *(const u32x4_t*)(kp + (int64_t)kvc * k_ss + col8 * 8);
-      vreg[c] = *(const u32x4_t*)(vp + (int64_t)kvc * v_ss + col8 * 8);
+      if (VSRC == 0)
+        vreg[c] = *(const u32x4_t*)(vp + (int64_t)kvc * v_ss + col8 * 8);
     }
   };
   auto write_lds = [&](int buf, const u32x4_t* kreg, const u32x4_t* vreg) {
@@ -420,7 +463,13 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
         const int byte = ba_swz<SWZ_K>(row * (2 * D) + col8 * 16, row);
         *(u32x4_t*)((char*)ldsK(buf) + byte) = kreg[c];
       }
-      if (VPATH == 0)
+      if (VSRC == 1) {
+        // the address ba_st_transposed gives these eight elements: the
+        // swizzle moves whole 16-byte granules, so the chunk stays whole
+        const int flat = tid + c * NT;
+        const int byte = ba_swz<SWZ_V, 7>(flat * 16, flat / (KVBLK / 8));
+        *(u32x4_t*)((char*)ldsVT(buf) + byte) = vreg[c];
+      } else if (VPATH == 0)
         ba_st_transposed<T, KVBLK, SWZ_V, 7>(ldsVT(buf), row, col8 * 8, vreg[c]);
       else
         ba_st_tr16row<T, D>(ldsVT(buf), row, col8 * 8, vreg[c]);
@@ -614,6 +663,12 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
     // For its D=128 carry-in form (the ring path) the result is the
     // placement the tuned numbers were measured at.  The pad is a few
     // s_nops executed once per workgroup.
+    // The header itself is not 128-byte aligned in any of these kernels
+    // (D=128 carry-in: 84 mod 128 with VSRC=0, 60 with VSRC=1).  For the
+    // VSRC=1 kernel, padding the preheader so that the header lands at 88
+    // or exactly 0 measured the same rate as 60, and 4 measured -2 %
+    // (profiles/fwd_vt/README.md): what matters is that the placement is
+    // a measured one and stays put, which this directive provides.
     asm volatile(".p2align 7");
     for (int tb = 0; tb < nt; tb += NBUF) {
       [[clang::always_inline]] tile_body(tb, ba_ic<0>{});
@@ -690,6 +745,46 @@ __global__ void attn_fwd_finalize_kernel(
         BA_LN2 * (m[((int64_t)b * N + n) * S + s] + log2f(lv));
 }
 
+// V^T image pre-pass (layout: vt_image.h).  One workgroup per (kv tile, kv
+// head, batch): the 64 x D tile goes through LDS with the transposed
+// staging write and the row-slice read the forward kernel uses for the same
+// image, so both global sides are 16 B per lane and coalesced.  Rows at
+// kv >= Sk are not read; their columns are written as zeros.  `img_elems`
+// is the capacity of `img` in elements: a chunk that would end past it is
+// not written.  Memory-bound, one pass over V in and one out.
+template <typename T, int D>
+__global__ __launch_bounds__(256) void attn_vt_image_kernel(
+    const T* __restrict__ v, T* __restrict__ img, int Sk, int Nk,
+    int64_t v_sb, int64_t v_ss, int64_t v_sh, int64_t img_elems) {
+  constexpr int KVBLK = BA_VT_KVBLK;
+  constexpr int NT = 256;
+  constexpr int PT = (KVBLK * D / 8) / NT;
+  __shared__ T lds[KVBLK * D];
+  const int tid = threadIdx.x;
+  const int t = blockIdx.x, nkv = blockIdx.y, b = blockIdx.z;
+  const T* vp = v + (int64_t)b * v_sb + (int64_t)nkv * v_sh;
+#pragma unroll
+  for (int c = 0; c < PT; ++c) {
+    const int flat = tid + c * NT;
+    const int row = flat / (D / 8), col8 = flat % (D / 8);
+    const int kvg = t * KVBLK + row;
+    u32x4_t chunk = {0, 0, 0, 0};
+    if (kvg < Sk)
+      chunk = *(const u32x4_t*)(vp + (int64_t)kvg * v_ss + col8 * 8);
+    ba_st_transposed<T, KVBLK, 7, 7>(lds, row, col8 * 8, chunk);
+  }
+  __syncthreads();
+  const int64_t blk = ba_vt_offset(Nk, Sk, D, b, nkv, (int64_t)t * KVBLK, 0);
+#pragma unroll
+  for (int c = 0; c < PT; ++c) {
+    const int flat = tid + c * NT;  // chunk (d = flat / 8, kv8 = flat % 8)
+    const auto f = ba_ld_rowslice<T, KVBLK, 7, 7>(lds, flat / (KVBLK / 8),
+                                                  (flat % (KVBLK / 8)) * 8);
+    const int64_t e = blk + (int64_t)flat * 8;
+    if (e + 8 <= img_elems) *(u32x4_t*)(img + e) = __builtin_bit_cast(u32x4_t, f);
+  }
+}
+
 }  // namespace
 
 extern "C" const char* bahip_last_error(void) { return ba_g_err; }
@@ -727,9 +822,9 @@ static dim3 fwd_grid(const fwd_args& a, int64_t B, int nt) {
 }
 
 template <typename T, int D, int OUT_STATE, int VPATH, int SUBT, int NT,
-          int NBUF, int KREG>
+          int NBUF, int KREG, int VSRC = 0>
 static void launch_fwd(const fwd_args& a, int64_t B, hipStream_t stream) {
-  attn_fwd_kernel<T, D, 64, OUT_STATE, VPATH, SUBT, NT, NBUF, KREG>
+  attn_fwd_kernel<T, D, 64, OUT_STATE, VPATH, SUBT, NT, NBUF, KREG, VSRC>
       <<<fwd_grid(a, B, NT), dim3(NT), 0, stream>>>(
           (const T*)a.q, (const T*)a.k, (const T*)a.v, a.o, a.lse, a.Sq, a.Sk,
           a.N, a.G, a.q_sb, a.q_ss, a.q_sh, a.k_sb, a.k_ss, a.k_sh, a.v_sb, a.v_ss,
@@ -737,11 +832,65 @@ static void launch_fwd(const fwd_args& a, int64_t B, hipStream_t stream) {
           a.a_sh, a.ml_sb, a.ml_sh, a.carry_in);
 }
 
+// The per-call knobs: the variant the BA_FWD_* table selects, and whether
+// a call with these shapes stages V from the V^T image (vt_image.h).
+// BA_FWD_VT=1 forces the image wherever the default variant runs, 0 forces
+// the in-kernel transpose, unset applies the auto rule; an experiment
+// variant always transposes in the kernel.
+static int fwd_read_knobs(int64_t Sq, int64_t G, ba_fwd_choice* c,
+                          bool* use_vt) {
+  ba_fwd_knobs kn;
+  kn.vpath = ba_env_int(BA_FWD_KNOB_SPECS[0].env, kn.vpath);
+  kn.subt = ba_env_int(BA_FWD_KNOB_SPECS[1].env, kn.subt);
+  kn.nt = ba_env_int(BA_FWD_KNOB_SPECS[2].env, kn.nt);
+  kn.nbuf = ba_env_int(BA_FWD_KNOB_SPECS[3].env, kn.nbuf);
+  kn.kreg = ba_env_int(BA_FWD_KNOB_SPECS[4].env, kn.kreg);
+  *c = ba_fwd_select(kn);
+  if (c->bad_knob)
+    return ba_fail(BAHIP_ERR_BAD_KNOB, "%s=%d is not an accepted value",
+                   c->bad_knob, c->bad_value);
+  const char* e = getenv("BA_FWD_VT");
+  const int vt = e ? e[0] - '0' : -1;  // "0" or "1", nothing else
+  if (e && !((vt == 0 || vt == 1) && e[1] == '\0'))
+    return ba_fail(BAHIP_ERR_BAD_KNOB, "BA_FWD_VT=%s is not an accepted value",
+                   e);
+  *use_vt = c->variant == BA_FWD_PRODUCTION &&
+            (vt < 0 ? ba_vt_reuse(Sq, G) >= BA_VT_AUTO_MIN_REUSE : vt == 1);
+  return 0;
+}
+
+// the pre-pass: img (capacity img_bytes) <- V^T image of v
+static int vt_image_entry(const void* v, void* img, int64_t img_bytes,
+                          int64_t B, int64_t Sk, int64_t Nk, int64_t D,
+                          const int64_t* vs, int dtype, void* stream) {
+  if (B < 1 || Sk < 1 || Nk < 1 || Nk > 65535 || B > 65535)
+    return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                   "V^T image: unsupported shape B=%d Sk=%d Nk=%d", (int)B,
+                   (int)Sk, (int)Nk);
+  if (!img || !ba_vt_workspace_fits(img_bytes, B, Nk, Sk, D))
+    return ba_fail(BAHIP_ERR_WORKSPACE,
+                   "V^T image workspace of %lld bytes is smaller than the "
+                   "%lld needed",
+                   (long long)img_bytes, (long long)ba_vt_bytes(B, Nk, Sk, D));
+  const dim3 grid((unsigned)ba_vt_tiles(Sk), (unsigned)Nk, (unsigned)B);
+  return ba_dispatch_td(D, dtype, [&](auto td) {
+    using T = typename decltype(td)::type;
+    attn_vt_image_kernel<T, decltype(td)::D>
+        <<<grid, 256, 0, (hipStream_t)stream>>>(
+            (const T*)v, (T*)img, (int)Sk, (int)Nk, vs[0], vs[1], vs[2],
+            img_bytes / (int64_t)sizeof(T));
+    return ba_launch_status();
+  });
+}
+
 // Shared body of every forward entry point (Nk = N for the equal-heads
 // symbols; the kernel gets the group size G = N / Nk).  out_state = 0: the
 // stateless tile (o, lse; state pointers null).  out_state = 1: the
 // carry-in accumulator (o/lse null), launched through hip_function when
 // one is given, else through the variant the BA_FWD_* knobs select.
+// ws / ws_bytes: workspace for the V^T image, or null: with one, a call the
+// knobs route to the image form runs the pre-pass and then the forward on
+// the same stream; without one every call transposes in the kernel.
 static int fwd_entry(void* hip_function, int out_state, const void* q,
                      const void* k, const void* v, float* o, float* lse,
                      int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk,
@@ -749,7 +898,7 @@ static int fwd_entry(void* hip_function, int out_state, const void* q,
                      const int64_t* vs, float scale, int causal, int dtype,
                      float* acc, float* m,
                      float* l, const int64_t* as, const int64_t* mls,
-                     int carry_in, void* stream) {
+                     int carry_in, void* ws, int64_t ws_bytes, void* stream) {
   if (causal && Sq != Sk)
     return ba_fail(BAHIP_ERR_CAUSAL_SHAPE,
                    "causal tiles require Sq == Sk (%d vs %d)", (int)Sq,
@@ -783,16 +932,32 @@ static int fwd_entry(void* hip_function, int out_state, const void* q,
                      hipGetErrorString(e));
     return ba_ok();
   }
-  ba_fwd_knobs kn;
-  kn.vpath = ba_env_int(BA_FWD_KNOB_SPECS[0].env, kn.vpath);
-  kn.subt = ba_env_int(BA_FWD_KNOB_SPECS[1].env, kn.subt);
-  kn.nt = ba_env_int(BA_FWD_KNOB_SPECS[2].env, kn.nt);
-  kn.nbuf = ba_env_int(BA_FWD_KNOB_SPECS[3].env, kn.nbuf);
-  kn.kreg = ba_env_int(BA_FWD_KNOB_SPECS[4].env, kn.kreg);
-  const ba_fwd_choice c = ba_fwd_select(kn);
-  if (c.bad_knob)
-    return ba_fail(BAHIP_ERR_BAD_KNOB, "%s=%d is not an accepted value",
-                   c.bad_knob, c.bad_value);
+  ba_fwd_choice c;
+  bool use_vt;
+  if (int rc = fwd_read_knobs(Sq, G, &c, &use_vt)) return rc;
+  if (use_vt && ws) {
+    if (int rc = vt_image_entry(v, ws, ws_bytes, B, Sk, Nk, D, vs, dtype,
+                                stream))
+      return rc;
+    // same kernarg list: v is the image, v_sb / v_sh its strides
+    fwd_args ai = a;
+    ai.v = ws;
+    ai.v_sb = ba_vt_batch_stride(Nk, Sk, D);
+    ai.v_ss = 0;
+    ai.v_sh = ba_vt_head_stride(Sk, D);
+    return ba_dispatch_td(D, dtype, [&](auto td) {
+      using T = typename decltype(td)::type;
+      constexpr int TD = decltype(td)::D;
+      constexpr ba_fwd_variant P = BA_FWD_PRODUCTION;
+      if (out_state)
+        launch_fwd<T, TD, 1, P.vpath, P.subt, P.nt, P.nbuf, P.kreg, 1>(
+            ai, B, (hipStream_t)stream);
+      else
+        launch_fwd<T, TD, 0, P.vpath, P.subt, P.nt, P.nbuf, P.kreg, 1>(
+            ai, B, (hipStream_t)stream);
+      return ba_launch_status();
+    });
+  }
   return ba_dispatch_td(D, dtype, [&](auto td) {
     using T = typename decltype(td)::type;
     constexpr int TD = decltype(td)::D;
@@ -817,7 +982,58 @@ extern "C" int bahip_attn_fwd_gqa(
     void* stream) {
   return fwd_entry(nullptr, 0, q, k, v, o, lse, B, Sq, Sk, N, Nk, D, q_strides,
                    k_strides, v_strides, softmax_scale, causal, dtype, nullptr,
-                   nullptr, nullptr, nullptr, nullptr, 0, stream);
+                   nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, stream);
+}
+
+extern "C" int bahip_attn_fwd_gqa_ws(
+    const void* q, const void* k, const void* v, float* o, float* lse,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    void* workspace, int64_t workspace_bytes, void* stream) {
+  return fwd_entry(nullptr, 0, q, k, v, o, lse, B, Sq, Sk, N, Nk, D, q_strides,
+                   k_strides, v_strides, softmax_scale, causal, dtype, nullptr,
+                   nullptr, nullptr, nullptr, nullptr, 0, workspace,
+                   workspace_bytes, stream);
+}
+
+extern "C" int bahip_attn_fwd_accum_gqa_ws(
+    void* hip_function, const void* q, const void* k, const void* v,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    float* acc, float* m, float* l, const int64_t acc_strides[3],
+    const int64_t ml_strides[2], int carry_in, void* workspace,
+    int64_t workspace_bytes, void* stream) {
+  return fwd_entry(hip_function, 1, q, k, v, nullptr, nullptr, B, Sq, Sk, N,
+                   Nk, D, q_strides, k_strides, v_strides, softmax_scale,
+                   causal, dtype, acc, m, l, acc_strides, ml_strides, carry_in,
+                   workspace, workspace_bytes, stream);
+}
+
+extern "C" int64_t bahip_attn_vt_image_bytes(int64_t B, int64_t Nk,
+                                             int64_t Sk, int64_t D) {
+  return ba_vt_bytes(B, Nk, Sk, D);
+}
+
+extern "C" int64_t bahip_attn_fwd_workspace_bytes(int64_t B, int64_t Sq,
+                                                  int64_t Sk, int64_t N,
+                                                  int64_t Nk, int64_t D) {
+  ba_fwd_choice c;
+  bool use_vt;
+  const int64_t G = ba_gqa_group(N, Nk);
+  // a bad knob or head pair is reported by the forward call itself
+  if (!G || fwd_read_knobs(Sq, G, &c, &use_vt) || !use_vt) return 0;
+  return ba_vt_bytes(B, Nk, Sk, D);
+}
+
+extern "C" int bahip_attn_vt_image(const void* v, void* image,
+                                   int64_t image_bytes, int64_t B, int64_t Sk,
+                                   int64_t Nk, int64_t D,
+                                   const int64_t v_strides[3], int dtype,
+                                   void* stream) {
+  return vt_image_entry(v, image, image_bytes, B, Sk, Nk, D, v_strides, dtype,
+                        stream);
 }
 
 extern "C" int bahip_attn_fwd_accum_gqa(
@@ -830,7 +1046,7 @@ extern "C" int bahip_attn_fwd_accum_gqa(
   return fwd_entry(hip_function, 1, q, k, v, nullptr, nullptr, B, Sq, Sk, N,
                    Nk, D, q_strides, k_strides, v_strides, softmax_scale,
                    causal, dtype, acc, m, l, acc_strides, ml_strides, carry_in,
-                   stream);
+                   nullptr, 0, stream);
 }
 
 // the equal-heads symbols: Nk = N

@@ -70,6 +70,17 @@ void check_qkv3(const at::Tensor& q, const at::Tensor& k,
                 bahip_last_error());                                       \
   } while (0)
 
+// Workspace for the V^T image of this call, or an undefined tensor where
+// the knobs and the auto rule keep the in-kernel transpose.  Allocated per
+// call on the current stream and never cached: the ring hands the same k/v
+// buffers in with new contents every round.
+at::Tensor fwd_workspace(const at::Tensor& q, const at::Tensor& k) {
+  const int64_t bytes = bahip_attn_fwd_workspace_bytes(
+      q.size(0), q.size(1), k.size(1), q.size(2), k.size(2), q.size(3));
+  if (bytes <= 0) return at::Tensor();
+  return at::empty({bytes}, q.options().dtype(at::kByte));
+}
+
 std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k,
                                  const at::Tensor& v, double softmax_scale,
                                  bool causal) {
@@ -78,13 +89,45 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k,
   const auto Sk = k.size(1);
   auto o = at::empty({B, Sq, N, D}, q.options().dtype(at::kFloat));
   auto lse = at::empty({B, N, Sq}, q.options().dtype(at::kFloat));
+  auto ws = fwd_workspace(q, k);
   auto stream = at::hip::getCurrentHIPStream().stream();
-  BA_CALL(bahip_attn_fwd_gqa(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                             o.data_ptr<float>(), lse.data_ptr<float>(), B,
-                             Sq, Sk, N, k.size(2), D, Strides3(q), Strides3(k),
-                             Strides3(v), (float)softmax_scale, causal ? 1 : 0,
-                             dtype_code(q), stream));
+  BA_CALL(bahip_attn_fwd_gqa_ws(
+      q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr<float>(),
+      lse.data_ptr<float>(), B, Sq, Sk, N, k.size(2), D, Strides3(q),
+      Strides3(k), Strides3(v), (float)softmax_scale, causal ? 1 : 0,
+      dtype_code(q), ws.defined() ? ws.data_ptr() : nullptr,
+      ws.defined() ? ws.numel() : 0, stream));
   return {o, lse};
+}
+
+// The V^T image of v ([B, Sk, Nk, D], strided) as a [B, Nk, T, D, 64]
+// tensor, T = ceil(Sk / 64): what the forward's pre-pass writes.
+at::Tensor attn_vt_image(const at::Tensor& v, c10::optional<at::Tensor> out) {
+  check_qkv(v, "v");
+  const auto B = v.size(0), Sk = v.size(1), Nk = v.size(2), D = v.size(3);
+  const int64_t T = (Sk + 63) / 64;
+  // `out` is either the image tensor itself or a flat workspace of v's
+  // dtype, handed to the C entry with its true size: whether it is large
+  // enough is the launcher's check (BAHIP_ERR_WORKSPACE), not this layer's.
+  at::Tensor img;
+  if (out.has_value()) {
+    img = *out;
+    TORCH_CHECK(img.is_cuda() && img.scalar_type() == v.scalar_type() &&
+                    img.is_contiguous() &&
+                    (img.dim() == 1 ||
+                     img.sizes() == at::IntArrayRef({B, Nk, T, D, 64})),
+                "image out must be contiguous, of v's dtype, and either "
+                "[B,Nk,ceil(Sk/64),D,64] or a flat workspace");
+  } else {
+    img = at::empty({B, Nk, T, D, 64}, v.options());
+  }
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  BA_CALL(bahip_attn_vt_image(v.data_ptr(), img.data_ptr(),
+                              img.numel() * img.element_size(), B, Sk, Nk, D,
+                              Strides3(v), dtype_code(v), stream));
+  if (img.dim() == 1) return img.narrow(0, 0, B * Nk * T * D * 64)
+                          .view({B, Nk, T, D, 64});
+  return img;
 }
 
 // Checks and stride extraction shared by attn_fwd_accum (asm_fn null: the
@@ -106,13 +149,16 @@ void fwd_accum_call(void* asm_fn, const at::Tensor& q, const at::Tensor& k,
   int64_t mls[2] = {m.stride(0), m.stride(1)};
   TORCH_CHECK(l.stride(0) == mls[0] && l.stride(1) == mls[1],
               "m/l stride mismatch");
+  // the module kernel transposes V itself: no workspace
+  auto ws = asm_fn ? at::Tensor() : fwd_workspace(q, k);
   auto stream = at::hip::getCurrentHIPStream().stream();
-  BA_CALL(bahip_attn_fwd_accum_gqa(
+  BA_CALL(bahip_attn_fwd_accum_gqa_ws(
       asm_fn, q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Sq, Sk, N,
       k.size(2), D, Strides3(q), Strides3(k), Strides3(v), (float)softmax_scale,
       causal ? 1 : 0, dtype_code(q), acc.data_ptr<float>(),
       m.data_ptr<float>(), l.data_ptr<float>(), Strides3(acc), mls,
-      carry_in ? 1 : 0, stream));
+      carry_in ? 1 : 0, ws.defined() ? ws.data_ptr() : nullptr,
+      ws.defined() ? ws.numel() : 0, stream));
 }
 
 void attn_fwd_accum(const at::Tensor& q, const at::Tensor& k,
@@ -291,6 +337,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "carry-in accumulator fwd tile (in-kernel LSE merge)");
   m.def("attn_fwd_finalize", &attn_fwd_finalize,
         "o = acc/l (cast), lse from state");
+  m.def("attn_vt_image", &attn_vt_image,
+        "V^T image [B,Nk,ceil(Sk/64),D,64] the forward's pre-pass writes",
+        py::arg("v"), py::arg("out") = py::none());
+  m.def("attn_fwd_workspace_bytes", &bahip_attn_fwd_workspace_bytes,
+        "V^T image bytes a forward of (B, Sq, Sk, N, Nk, D) allocates under "
+        "the current knobs; 0 = in-kernel transpose");
   m.def("attn_bwd_preprocess", &attn_bwd_preprocess, "delta = rowsum(o*do)",
         py::arg("o"), py::arg("dout"), py::arg("out") = py::none());
   m.def("attn_bwd", &attn_bwd, "BurstAttention bwd tile (gfx950)");

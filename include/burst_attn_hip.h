@@ -66,6 +66,8 @@ extern "C" {
 #define BAHIP_ERR_BAD_KNOB 1004       /* a BA_FWD_* knob, BA_BWD_FUSED,
                                          BA_BWD_DK_FLIP, BA_DQ_PIPE or
                                          BA_DKQ_DBG outside its set */
+#define BAHIP_ERR_WORKSPACE 1005      /* V^T image workspace null or too
+                                         small; nothing is launched */
 
 const char* bahip_last_error(void);
 
@@ -128,6 +130,58 @@ int bahip_attn_fwd_accum_gqa(
     const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
     float* acc, float* m, float* l, const int64_t acc_strides[3],
     const int64_t ml_strides[2], int carry_in, void* stream);
+
+/* ---- V^T image (burst_attn_amd/csrc/vt_image.h) -----------------------
+ * The forward stages V into LDS transposed.  Every workgroup that visits a
+ * kv tile repeats that transpose, ceil(Sq/256) * G times per tile; with a
+ * workspace the forward instead runs a pre-pass that writes the transposed
+ * tiles once ([B][Nk][ceil(Sk/64)][D][64] elements, pad columns zero) and
+ * then copies them.  Results are bitwise those of the plain entry points.
+ *
+ * bahip_attn_vt_image_bytes: byte size of the image of a [B, Sk, Nk, D] V.
+ * bahip_attn_fwd_workspace_bytes: what a forward call with these shapes
+ *   wants as workspace under the current knobs: the image size where the
+ *   image form would run, else 0 (BA_FWD_VT=0, an experiment variant, or
+ *   BA_FWD_VT unset and ceil(Sq/256) * G below the measured threshold).
+ * bahip_attn_fwd_gqa_ws / bahip_attn_fwd_accum_gqa_ws: the *_gqa forwards
+ *   with a workspace.  A null workspace is the plain entry point.  With one,
+ *   a call that the knobs route to the image form launches the pre-pass and
+ *   then the forward on `stream`; the image is rebuilt on every call, and the
+ *   workspace may be reused or freed (stream-ordered) once the call is
+ *   enqueued.  A call routed to the in-kernel transpose ignores it.  A
+ *   workspace smaller than bahip_attn_vt_image_bytes returns
+ *   BAHIP_ERR_WORKSPACE and launches nothing.  A module kernel
+ *   (hip_function non-null) always transposes in the kernel.
+ * bahip_attn_vt_image: the pre-pass alone; v strided {batch, seq, head}.
+ * BA_FWD_VT: 1 forces the image form wherever the default variant runs and
+ *   a workspace is given, 0 forces the in-kernel transpose, unset is the auto
+ *   rule; any other value returns BAHIP_ERR_BAD_KNOB. */
+int64_t bahip_attn_vt_image_bytes(int64_t B, int64_t Nk, int64_t Sk,
+                                  int64_t D);
+int64_t bahip_attn_fwd_workspace_bytes(int64_t B, int64_t Sq, int64_t Sk,
+                                       int64_t N, int64_t Nk, int64_t D);
+int bahip_attn_vt_image(
+    const void* v, void* image, int64_t image_bytes,
+    int64_t B, int64_t Sk, int64_t Nk, int64_t D,
+    const int64_t v_strides[3], int dtype, void* stream);
+int bahip_attn_fwd_gqa_ws(
+    const void* q, const void* k, const void* v,
+    float* o, float* lse,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3],
+    const int64_t k_strides[3],
+    const int64_t v_strides[3],
+    float softmax_scale, int causal, int dtype,
+    void* workspace, int64_t workspace_bytes, void* stream);
+int bahip_attn_fwd_accum_gqa_ws(
+    void* hip_function,
+    const void* q, const void* k, const void* v,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    float* acc, float* m, float* l, const int64_t acc_strides[3],
+    const int64_t ml_strides[2], int carry_in,
+    void* workspace, int64_t workspace_bytes, void* stream);
 
 /* o = acc / l cast to dtype; lse = ln(l) + m*ln2; contiguous full chunk */
 int bahip_attn_fwd_finalize(
