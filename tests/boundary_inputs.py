@@ -35,6 +35,10 @@ __all__ = [
     "KNOB_CASES",
     "make_inputs",
     "round2_kv",
+    "DOMINATED_GAIN",
+    "DOMINATED_MIN_GAP",
+    "DOMINATED_CASES",
+    "dominated_kv",
     "case_id",
     "dtype_name",
     "K_POISON",
@@ -108,7 +112,21 @@ def seam_weighted(b, sq, sk, n, nk, d, dtype, seed, beta=None, gain=DO_GAIN):
     return tuple(t.to(dtype) for t in (q, k, v, do))
 
 
-def diag_needle(b, s, n, nk, d, dtype, seed, a=None, c=None):
+def _rows_from(t, shift):
+    """out[:, j] = t[:, j + shift]; rows outside the sequence are zero."""
+    if shift == 0:
+        return t
+    out = torch.zeros_like(t)
+    s = t.shape[1]
+    if abs(shift) < s:
+        if shift > 0:
+            out[:, :s - shift] = t[:, shift:]
+        else:
+            out[:, -shift:] = t[:, :s + shift]
+    return out
+
+
+def diag_needle(b, s, n, nk, d, dtype, seed, a=None, c=None, lag=0):
     """Causal family: k_j = eps_j + a q_j / sqrt(d) + c q_{j-1} / sqrt(d).
 
     q rows are normalised to |q|^2 = d, so score(i, i) = a and
@@ -117,6 +135,14 @@ def diag_needle(b, s, n, nk, d, dtype, seed, a=None, c=None):
     of its mass.  c = 2a: the first super-diagonal key would swamp the row
     if it leaked through the mask.  With grouped heads KV head h is built
     from its group's first query head.  Returns (q, k, v, do).
+
+    With `lag` the hot allowed key sits `lag` tokens behind the row and the
+    forbidden one max(lag, 1) ahead of it,
+        k_j = eps_j + a q_{j+lag} / sqrt(d) + c q_{j-max(lag,1)} / sqrt(d),
+    rows outside the sequence contributing zero.  Chunked over W ring ranks
+    those keys belong to another rank: they are the boundary pairs of the
+    ring's cross-rank tiles (tests/ring_rounds.py).  lag = 0 is the family
+    above, bit for bit.
     """
     if a is None:
         a = math.log(max(s, 2))
@@ -129,9 +155,9 @@ def diag_needle(b, s, n, nk, d, dtype, seed, a=None, c=None):
     v = _randn(g, b, s, nk, d)
     do = _randn(g, b, s, n, d)
     qh = q[:, :, :: n // nk]  # the group's first query head, [B,S,Nk,D]
-    q_prev = torch.zeros_like(qh)
-    q_prev[:, 1:] = qh[:, :-1]
-    k = eps + (a / math.sqrt(d)) * qh + (c / math.sqrt(d)) * q_prev
+    q_hot = _rows_from(qh, lag)
+    q_prev = _rows_from(qh, -max(lag, 1))
+    k = eps + (a / math.sqrt(d)) * q_hot + (c / math.sqrt(d)) * q_prev
     return tuple(t.to(dtype) for t in (q, k, v, do))
 
 
@@ -262,6 +288,29 @@ def round2_kv(case, dtype):
                                case.d, dtype, 9001 + case.sk + case.d,
                                beta=beta)
     return k, v
+
+
+# Dominated rounds: round2_kv moved along the seam direction until a causal
+# carry-in round on them lies wholly below ("below") or above ("above") what
+# the state carries.  A key's score moves by gain (1 + z / sqrt(d)), z ~
+# N(0, 1) from q's own component along u (|z| reaches 3.5 over the rows);
+# 80 leaves every second-round score of a row at least 30 from the row's
+# carried max at d = 64 and 128 (tests/test_boundary_inputs_cpu.py), and at
+# most 130: exp2(-130 log2 e) is 0 in fp32, the carried side must vanish.
+DOMINATED_GAIN = 80.0
+DOMINATED_MIN_GAP = 30.0
+DOMINATED_CASES = [c for c in CASES
+                   if c.family == "seam_weighted" and c.causal
+                   and c.sq == 328 and (c.n, c.nk) == (4, 2)]
+
+
+def dominated_kv(case, dtype, which):
+    """(k, v) of a second round whose every score is DOMINATED_MIN_GAP or
+    more below / above the first round's row max."""
+    sign = {"below": -1.0, "above": 1.0}[which]
+    k2, v2 = round2_kv(case, torch.float32)
+    k2 = k2 + sign * (DOMINATED_GAIN / math.sqrt(case.d)) * seam_vector(case.d)
+    return k2.to(dtype), v2.to(dtype)
 
 
 def dtype_name(dtype):

@@ -25,8 +25,10 @@ def _merge_full(P, o, lse, o_i, lse_i):
 
 
 def simulate_ring(P, q_full, k_full, v_full, do_full, W, scale, causal,
-                  striped=False, optimize_bwd_comm=False):
-    """Returns (o_full, dq_full, dk_full, dv_full) reassembled."""
+                  striped=False, optimize_bwd_comm=False, return_lse=False):
+    """Returns (o_full, dq_full, dk_full, dv_full) reassembled; with
+    return_lse also the merged lse [B, N, S] as a fifth item.  k/v may
+    carry fewer heads than q where the provider's tiles take them."""
     zig = causal and not striped
     dim = 1
     ch = lambda t, r: get_chunk(t, dim, r, W, zigzag=zig, striped=striped)
@@ -113,4 +115,7 @@ def simulate_ring(P, q_full, k_full, v_full, do_full, W, scale, causal,
                     dvs[rank][:, :half] += dv_i
 
     un = lambda lst: unchunk([t for t in lst], dim, zigzag=zig, striped=striped)
-    return un(os_), un(dqs), un(dks), un(dvs)
+    out = un(os_), un(dqs), un(dks), un(dvs)
+    if return_lse:
+        out += (unchunk(lses, 2, zigzag=zig, striped=striped),)
+    return out

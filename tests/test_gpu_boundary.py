@@ -11,6 +11,13 @@ the two-call carry-in form with the same second-round keys
 (``boundary_inputs.round2_kv``), and the backward, with the two exceptions
 its docstring lists.  The poisoned-parent tests reuse the same tensors.
 
+The ring's later rounds hand the kernels forms of their own, run here at
+tile level on the same cases (tests/test_gpu_ring_rounds.py runs whole
+rings of them): the causal carry-in call, the call on views shifted by
+one token, the rescale of carried state by a round that dominates it or
+is dominated by it, and the backward under an lse and delta that belong to
+more keys than the tile's.
+
 Every forward knob set of FWD_ALT_KNOBS (test_gpu_parity.py) and every
 backward knob of BWD_KNOBS below is run against the oracle at S=328, at
 head_dim 64 and 128 (separate kernel instantiations); a new knob value
@@ -27,8 +34,12 @@ import torch
 from . import boundary_inputs as bi
 from .boundary_inputs import case_id as _id, dtype_name as _dt
 from .boundary_refs import (bwd_ref as _bwd_ref, carry_ref as _carry_ref,
+                            dominated_kv as _dominated_kv,
+                            dominated_ref as _dominated_ref,
                             fwd_ref as _fwd_ref, gates, inputs as _inputs,
-                            round2_kv as _round2_kv, scale_of as _scale)
+                            merged_bwd_ref as _merged_bwd_ref,
+                            round2_kv as _round2_kv, scale_of as _scale,
+                            shifted_ref as _shifted_ref)
 from .mutant_oracle import gate_ratio
 from .test_gpu_parity import FWD_ALT_KNOBS
 
@@ -51,8 +62,10 @@ def _gpu(*ts):
 
 
 def _check(test, case, dtype, outs, refs):
-    """Print every output's worst gate ratio, then assert the gates."""
+    """Print every output's worst gate ratio, then assert the gates (a
+    second round's dk2/dv2 under the dk/dv gates)."""
     gt = gates(dtype, case.n // case.nk)
+    gt.update(dk2=gt["dk"], dv2=gt["dv"])
     pairs = [(name, outs[name].float().cpu(), refs[name]) for name in outs]
     for name, out, ref in pairs:
         print(f"GATE {test} {_id(case)} {_dt(dtype)} {name} "
@@ -108,6 +121,79 @@ def test_fwd_carry_in(case, dtype):
            _named(_carry_ref(case, dtype)))
 
 
+# ---- forward: the carry-in forms of the ring's later rounds.  The striped
+# ring's rounds 2..W are CAUSAL carry-in calls, half of them on views
+# shifted by one token, whose m/l rows start 4 bytes into the parent's.
+
+CAUSAL_CASES = pytest.mark.parametrize(
+    "case", [c for c in bi.CASES if c.causal], ids=_id)
+SHIFT_CASES = pytest.mark.parametrize(
+    "case", [c for c in bi.CASES if c.causal and c.sq >= 2], ids=_id)
+
+
+@BY_DTYPE
+@CAUSAL_CASES
+def test_fwd_carry_in_causal(case, dtype):
+    """The striped order, the reverse of _carry_in: a fresh unmasked round
+    on round2_kv, then the case's keys merged in under the causal mask.
+    The merge does not depend on the order, so the reference is the same."""
+    ext = _ext()
+    q, k, v, _ = _gpu(*_inputs(case, dtype))
+    k2, v2 = _gpu(*_round2_kv(case, dtype))
+    acc, m, l = _state(case.b, case.sq, case.n, case.d)
+    ext.attn_fwd_accum(q, k2, v2, _scale(case), False, acc, m, l, False)
+    ext.attn_fwd_accum(q, k, v, _scale(case), True, acc, m, l, True)
+    o, lse = ext.attn_fwd_finalize(acc, m, l, dtype)
+    _check("carry-causal", case, dtype, {"o": o, "lse": lse},
+           _named(_carry_ref(case, dtype)))
+
+
+def _shifted_state(case, dtype):
+    """(acc, m, l) after a fresh causal round on (k, v) and the shifted
+    causal carry-in round on round2_kv (tile_window's striped later-rank
+    window)."""
+    ext = _ext()
+    q, k, v, _ = _gpu(*_inputs(case, dtype))
+    k2, v2 = _gpu(*_round2_kv(case, dtype))
+    acc, m, l = _state(case.b, case.sq, case.n, case.d)
+    ext.attn_fwd_accum(q, k, v, _scale(case), True, acc, m, l, False)
+    ext.attn_fwd_accum(q[:, 1:], k2[:, :-1], v2[:, :-1], _scale(case), True,
+                       acc[:, 1:], m[:, :, 1:], l[:, :, 1:], True)
+    return acc, m, l
+
+
+@BY_DTYPE
+@SHIFT_CASES
+def test_fwd_carry_in_shifted(case, dtype):
+    o, lse = _ext().attn_fwd_finalize(*_shifted_state(case, dtype), dtype)
+    _check("carry-shifted", case, dtype, {"o": o, "lse": lse},
+           _named(_shifted_ref(case, dtype)))
+
+
+@pytest.mark.parametrize("which", ["below", "above"])
+@BY_DTYPE
+@pytest.mark.parametrize("case", bi.DOMINATED_CASES, ids=_id)
+def test_fwd_carry_in_dominated(case, dtype, which):
+    """The exp2-domain rescale of carried state at its ends: a causal
+    carry-in round whose every score is 30 or more below the carried max
+    (the result is round 1, to within the gate) or above it (the carried
+    acc and l must vanish without leaving inf or nan behind)."""
+    ext = _ext()
+    q, k, v, _ = _gpu(*_inputs(case, dtype))
+    k2, v2 = _gpu(*_dominated_kv(case, dtype, which))
+    acc, m, l = _state(case.b, case.sq, case.n, case.d)
+    ext.attn_fwd_accum(q, k, v, _scale(case), True, acc, m, l, False)
+    ext.attn_fwd_accum(q, k2, v2, _scale(case), True, acc, m, l, True)
+    o, lse = ext.attn_fwd_finalize(acc, m, l, dtype)
+    for name, t in (("acc", acc), ("m", m), ("l", l), ("o", o), ("lse", lse)):
+        assert bool(torch.isfinite(t).all()), name
+    _check(f"carry-dominated-{which}", case, dtype, {"o": o, "lse": lse},
+           _named(_dominated_ref(case, dtype, which)))
+    if which == "below":
+        _check("carry-dominated-below-vs-round1", case, dtype,
+               {"o": o, "lse": lse}, _named(_fwd_ref(case, dtype)))
+
+
 @FWD_ALT_KNOBS
 @BY_DTYPE
 @KNOB_CASES
@@ -155,6 +241,33 @@ BY_DET = pytest.mark.parametrize("det", [False, True],
 def test_bwd_default_plan(case, dtype, det):
     _check("bwd", case, dtype, _bwd(case, dtype, det),
            _named_grads(_bwd_ref(case, dtype)))
+
+
+@BY_DET
+@BY_DTYPE
+@SHIFT_CASES
+def test_bwd_accum_under_merged_lse(case, dtype, det):
+    """The backward as the ring calls it: lse and delta belong to the
+    merged two-round forward of test_fwd_carry_in_shifted, not to the tile
+    being differentiated, so a tile's P is a fragment of a row; both
+    rounds' tiles accumulate into one dq, the second through the shifted
+    views delta[:, :, 1:], lse[:, :, 1:], dq[:, 1:] and dk2/dv2[:, :-1]."""
+    ext = _ext()
+    q, k, v, do = _gpu(*_inputs(case, dtype))
+    k2, v2 = _gpu(*_round2_kv(case, dtype))
+    o, lse = ext.attn_fwd_finalize(*_shifted_state(case, dtype), dtype)
+    delta = ext.attn_bwd_preprocess(o, do)
+    zeros = lambda t: torch.zeros(t.shape, dtype=torch.float32, device="cuda")
+    dq, dk, dv, dk2, dv2 = zeros(q), zeros(k), zeros(v), zeros(k2), zeros(v2)
+    sc = _scale(case)
+    ext.attn_bwd_accum(do, q, k, v, delta, lse, sc, True, det, dq, dk, dv)
+    ext.attn_bwd_accum(do[:, 1:], q[:, 1:], k2[:, :-1], v2[:, :-1],
+                       delta[:, :, 1:], lse[:, :, 1:], sc, True, det,
+                       dq[:, 1:], dk2[:, :-1], dv2[:, :-1])
+    names = ("dq", "dk", "dv", "dk2", "dv2")
+    _check("bwd-merged-lse", case, dtype,
+           dict(zip(names, (dq, dk, dv, dk2, dv2))),
+           dict(zip(names, _merged_bwd_ref(case, dtype))))
 
 
 # (knob, value, needs equal heads): the experiment plans of bwd_plans.h.
