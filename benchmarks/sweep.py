@@ -15,6 +15,15 @@ counted on the query heads; fewer K/V bytes) and the backward tile both
 as the in-kernel group loop and as the G-launch comparator.  --kv-heads
 also applies to the other burst configs.
 
+Packed sequences (segment ids):
+  python benchmarks/sweep.py --configs packed --doc-len 8192
+runs, at --seq (65536), dense causal, the packed causal sequence of
+--doc-len documents (repeat the option or give a comma list for mixed
+lengths, cycled until the sequence is full), for one uniform length the
+b = seq / doc-len batch of single documents (the same visible work), and
+the segment pre-pass alone at 65536 and 1048576 tokens.  TFLOPS of the
+packed rows count the visible pairs only.
+
 Row fields mirror the reference's results_torch.jsonl semantics.
 """
 
@@ -91,6 +100,67 @@ def bench_burst(args, b, s_global, n, d, causal, striped, opt_bwd, steps, warmup
         "fwdbwd_ms": round(t_fb * 1e3, 2),
         "fwdbwd_tflops_per_gpu": round(3.5 * f / t_fb / 1e12 / world, 2),
     }
+
+
+def packed_cu(s, doc_lens):
+    """cu_seqlens of `doc_lens` cycled until s tokens are covered (the last
+    document is cut at s)."""
+    cu, i = [0], 0
+    while cu[-1] < s:
+        cu.append(min(s, cu[-1] + doc_lens[i % len(doc_lens)]))
+        i += 1
+    return cu
+
+
+def bench_packed(args, s, n, nk, d, doc_lens, steps, warmup):
+    """Causal forward and forward+backward of one packed sequence through
+    burst_attn_func(segment_ids=...)."""
+    from burst_attn_amd import burst_attn_func, segment_ids_from_cu_seqlens
+
+    dtype = torch.float16 if args.dtype == "fp16" else torch.bfloat16
+    g = torch.Generator().manual_seed(1000)
+    mk = lambda h=n: torch.randn(1, s, h, d, generator=g).to(dtype).cuda()
+    q, k, v, do = mk(), mk(nk), mk(nk), mk()
+    cu = packed_cu(s, doc_lens)
+    ids = segment_ids_from_cu_seqlens(cu, s).unsqueeze(0).cuda()
+
+    def fwd():
+        with torch.no_grad():
+            burst_attn_func(q, k, v, None, "cuda", True, segment_ids=ids)
+
+    def fwdbwd():
+        qg, kg, vg = (t.detach().requires_grad_() for t in (q, k, v))
+        o = burst_attn_func(qg, kg, vg, None, "cuda", True, segment_ids=ids)
+        torch.autograd.grad(o, (qg, kg, vg), do)
+
+    t_f = timeit(fwd, steps, warmup)
+    t_fb = timeit(fwdbwd, steps, warmup)
+    pairs = sum((b - a) * (b - a) for a, b in zip(cu[:-1], cu[1:])) / 2
+    f = 4.0 * pairs * n * d
+    return {
+        "method": "burst_packed", "b": 1, "s": s, "n": n, "nk": nk, "d": d,
+        "causal": True, "doc_lens": doc_lens, "docs": len(cu) - 1,
+        "visible_frac": round(pairs / (s * s / 2), 4), "wsize": 1,
+        "dtype": args.dtype,
+        "fwd_ms": round(t_f * 1e3, 2),
+        "fwd_tflops_per_gpu": round(f / t_f / 1e12, 2),
+        "fwdbwd_ms": round(t_fb * 1e3, 2),
+        "fwdbwd_tflops_per_gpu": round(3.5 * f / t_fb / 1e12, 2),
+    }
+
+
+def bench_seg_prepass(args, s, doc_len, steps, warmup):
+    """The segment pre-pass alone (both side pairs, as the backward runs
+    it; the forward runs half of it)."""
+    from burst_attn_amd import segment_ids_from_cu_seqlens
+    from burst_attn_amd._ext import load_extension
+
+    ext = load_extension()
+    ids = segment_ids_from_cu_seqlens(packed_cu(s, [doc_len]), s)
+    ids = ids.unsqueeze(0).cuda()
+    t = timeit(lambda: ext.attn_seg_prepass(ids, ids), steps, warmup)
+    return {"method": "seg_prepass", "b": 1, "s": s, "doc_lens": [doc_len],
+            "wsize": 1, "prepass_us": round(t * 1e6, 1)}
 
 
 def bench_bwd_tile(args, b, s, n, nk, d, causal, g_launch, steps, warmup):
@@ -204,7 +274,8 @@ def bench_ring_naive(args, b, s_global, n, d, steps, warmup):
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--configs",
-                   choices=["quick", "ring", "batch", "single", "naive", "gqa"],
+                   choices=["quick", "ring", "batch", "single", "naive", "gqa",
+                            "packed"],
                    default="quick")
     p.add_argument("--steps", type=int, default=3)
     p.add_argument("--warmup", type=int, default=1)
@@ -214,7 +285,10 @@ def main():
     p.add_argument("--kv-heads", type=int, default=None,
                    help="K/V heads (default: equal to --heads)")
     p.add_argument("--seq", type=int, default=65536,
-                   help="sequence length of the gqa config")
+                   help="sequence length of the gqa and packed configs")
+    p.add_argument("--doc-len", action="append", default=None,
+                   help="packed config: document length(s); repeat or give "
+                        "a comma list for mixed lengths (default 8192)")
     args = p.parse_args()
     nk = args.heads if args.kv_heads is None else args.kv_heads
     if nk < 1 or args.heads % nk:
@@ -273,6 +347,25 @@ def main():
                     rows.append(bench_bwd_tile(args, 1, args.seq, n, nk, d,
                                                causal, g_launch, args.steps,
                                                args.warmup))
+
+    elif args.configs == "packed":
+        if world != 1:
+            p.error("--configs packed is a one-GPU config")
+        doc_lens = [int(x) for item in (args.doc_len or ["8192"])
+                    for x in item.split(",")]
+        if min(doc_lens) < 1:
+            p.error("--doc-len must be positive")
+        s = args.seq
+        rows.append(bench_burst(args, 1, s, n, d, True, False, False,
+                                args.steps, args.warmup, nk))
+        if len(doc_lens) == 1 and s % doc_lens[0] == 0:
+            rows.append(bench_burst(args, s // doc_lens[0], doc_lens[0], n, d,
+                                    True, False, False, args.steps,
+                                    args.warmup, nk))
+        rows.append(bench_packed(args, s, n, nk, d, doc_lens, args.steps,
+                                 args.warmup))
+        for sp in (65536, 1048576):
+            rows.append(bench_seg_prepass(args, sp, doc_lens[0], 20, 3))
 
     if rank == 0:
         with open(args.out, "a") as f:

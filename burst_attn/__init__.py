@@ -8,5 +8,7 @@ from burst_attn_amd import (  # noqa: F401
     burst_attn_func_striped,
     OpBurstAttn,
     OpBurstAttnStrip,
+    local_segment_ids,
+    segment_ids_from_cu_seqlens,
 )
 from burst_attn_amd import comm  # noqa: F401

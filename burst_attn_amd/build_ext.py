@@ -122,12 +122,14 @@ def _build_asm_hsaco(verbose, force):
     # NBUF=2 production instantiations, accum form, fp16 and bf16).  The
     # last argument is VSRC=0: the module path launches the kernel that
     # transposes V itself, with today's fwd_args (the VSRC=1 twin reads the
-    # V^T image and differs only in that last Li1E).
+    # V^T image and differs only in that last Li1E).  The JE after it is
+    # the empty segment-id parameter pack: the segment form (J11ba_seg_argsE)
+    # is not a module kernel.
     text = open(s_path).read()
     names = {}
     for key, pat in (
-        ("f16_accum", r"_ZN12_GLOBAL__N_115attn_fwd_kernelIDF16_Li128ELi64ELi1ELi0ELi1ELi512ELi2ELi0ELi0EE\S*"),
-        ("bf16_accum", r"_ZN12_GLOBAL__N_115attn_fwd_kernelIDF16bLi128ELi64ELi1ELi0ELi1ELi512ELi2ELi0ELi0EE\S*"),
+        ("f16_accum", r"_ZN12_GLOBAL__N_115attn_fwd_kernelIDF16_Li128ELi64ELi1ELi0ELi1ELi512ELi2ELi0ELi0EJEE\S*"),
+        ("bf16_accum", r"_ZN12_GLOBAL__N_115attn_fwd_kernelIDF16bLi128ELi64ELi1ELi0ELi1ELi512ELi2ELi0ELi0EJEE\S*"),
     ):
         m = re.search(r"\.globl\t(" + pat + ")", text)
         if m:

@@ -31,6 +31,7 @@
 #include "attn_host.h"
 #include "bwd_plans.h"
 #include "gqa_heads.h"
+#include "seg_support.h"
 
 namespace {
 
@@ -69,7 +70,11 @@ constexpr int KVBLK = 64;
 // dO fragments move from 32 registers to a persistent LDS image, and
 // the freed registers hold a 2-deep software pipeline of the k/v
 // fragment reads so each ds_read has >= 2 MFMAs of cover.
-template <typename T, int D, int DQP = 0>
+// SEG: empty = the plain kernel; one ba_seg_args = the segment-id form
+// (attn_common.h; the forward's rules: id equality in `valid`, the block's
+// kv tile range from the pre-pass, per-wave tile skip by (min, max), an
+// empty range leaves before the first barrier having added nothing).
+template <typename T, int D, int DQP = 0, typename... SEG>
 __global__ __launch_bounds__(512) void bwd_dq_kernel(
     const T* __restrict__ dout, const T* __restrict__ q,
     const T* __restrict__ k, const T* __restrict__ v,
@@ -81,9 +86,12 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
     int64_t v_sb, int64_t v_ss, int64_t v_sh,
     int64_t d_sb, int64_t d_sh, int64_t l_sb, int64_t l_sh,
     int64_t dq_sb, int64_t dq_ss, int64_t dq_sh,
-    float scale, int causal) {
+    float scale, int causal, SEG... seg) {
   using MT = mfma_traits<T>;
   using frag = typename MT::frag;
+  constexpr bool HAS_SEG = sizeof...(SEG) != 0;
+  static_assert(!HAS_SEG || (sizeof...(SEG) == 1 && DQP == 0),
+                "segment ids: the default dq kernel");
   constexpr int SWZ = (D == 128) ? 15 : 7;   // row-major images (2*D B rows)
   constexpr int SWZ_T = 7;                   // transposed images (128 B rows)
   constexpr int NT = 512;
@@ -154,7 +162,24 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
   for (int dt = 0; dt < D / 32; ++dt) dqt[dt] = (f32x16_t)(0.f);
 
   const int kv_limit = causal ? min(Sk, (int)(blockIdx.x + 1) * 256) : Sk;
-  const int nt = (kv_limit + KVBLK - 1) / KVBLK;
+  const int nt_shape = (kv_limit + KVBLK - 1) / KVBLK;
+  int2 trange = {0, nt_shape};
+  int qid = 0, wq_min = 0, wq_max = 0;
+  const int32_t* kseg = nullptr;
+  const int2* tmm = nullptr;
+  if constexpr (HAS_SEG) {
+    const ba_seg_args sg = ba_seg_of(seg...);
+    const int2 r = sg.blk_range[(int64_t)b * gridDim.x + blockIdx.x];
+    trange.x = r.x;
+    trange.y = min(trange.y, r.y);
+    if (trange.x >= trange.y) return;  // workgroup-uniform, no barrier yet
+    qid = sg.q_seg[b * sg.q_sb + min(q_row, Sq - 1)];
+    ba_wave_minmax(qid, wq_min, wq_max);
+    kseg = sg.kv_seg + b * sg.kv_sb;
+    tmm = sg.tile_mm + (int64_t)b * ((Sk + KVBLK - 1) / KVBLK);
+  }
+  const int t_first = HAS_SEG ? trange.x : 0;
+  const int nt = HAS_SEG ? trange.y : nt_shape;
 
   auto issue_loads = [&](int tile, u32x4_t* kreg, u32x4_t* vreg) {
     const int kv0 = tile * KVBLK;
@@ -184,7 +209,7 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
 
   {
     u32x4_t kreg[PT], vreg[PT];
-    issue_loads(0, kreg, vreg);
+    issue_loads(t_first, kreg, vreg);
     write_lds(0, kreg, vreg);
     __syncthreads();
   }
@@ -192,13 +217,22 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
     __builtin_amdgcn_s_setprio(1);  // T5 static form (younger half)
 
   int cur = 0;
-  for (int t = 0; t < nt; ++t) {
+  for (int t = t_first; t < nt; ++t) {
     const int kv0 = t * KVBLK;
     const bool has_next = (t + 1) < nt;
     u32x4_t kreg[PT], vreg[PT];
     if (has_next) issue_loads(t + 1, kreg, vreg);
 
-    const bool active = !causal || (kv0 <= qb + 31);
+    bool active, seg_mask = false;
+    if constexpr (HAS_SEG) {
+      // segment form: the tile's (min, max) ids against the wave's
+      const int2 mm = tmm[t];
+      seg_mask = !(mm.x == mm.y && wq_min == wq_max && mm.x == wq_min);
+      active = (!causal || (kv0 <= qb + 31)) && mm.y >= wq_min &&
+               mm.x <= wq_max;
+    } else {
+      active = !causal || (kv0 <= qb + 31);
+    }
     if (active) {
 #pragma unroll
       for (int kvs = 0; kvs < 2; ++kvs) {
@@ -242,8 +276,10 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int kv_g = kv0 + kvs * 32 + ba_crow(r, 0) + 4 * hi;
-          const bool valid =
+          bool valid =
               kv_g < Sk && (!causal || kv_g <= q_row) && q_row < Sq;
+          if constexpr (HAS_SEG)
+            valid = valid && (!seg_mask || kseg[min(kv_g, Sk - 1)] == qid);
           const float e = valid ? __builtin_fmaf(st[r], c2, -lse2) : BA_NEG_BIG;
           const float p = ba_exp2(e);
           st[r] = p * (dpt[r] - dlt) * scale;
@@ -299,7 +335,13 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
 //   tiles ascending), so the result stays bitwise deterministic.  A
 //   template parameter rather than a runtime G = 1 so the equal-heads
 //   instantiation keeps its register allocation (the dK kernel is tight).
-template <typename T, int D, int MODE, int QBLK = 64, int GQA = 0>
+// SEG: empty = the plain kernel; one ba_seg_args = the segment-id form
+// (attn_common.h), the dq kernel's with the sides swapped: the lane's kv id
+// against the q ids of a tile, the block's q tile range from the pre-pass
+// (the same for every member of a group, so the flattened stream and its
+// "next head's first tile" prefetch only see another t0 and nt).
+template <typename T, int D, int MODE, int QBLK = 64, int GQA = 0,
+          typename... SEG>
 __global__ __launch_bounds__(512) void bwd_dkv_kernel(
     const T* __restrict__ dout, const T* __restrict__ q,
     const T* __restrict__ k, const T* __restrict__ v,
@@ -311,9 +353,12 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
     int64_t v_sb, int64_t v_ss, int64_t v_sh,
     int64_t d_sb, int64_t d_sh, int64_t l_sb, int64_t l_sh,
     int64_t o_sb, int64_t o_ss, int64_t o_sh,
-    float scale, int causal) {
+    float scale, int causal, SEG... seg) {
   using MT = mfma_traits<T>;
   using frag = typename MT::frag;
+  constexpr bool HAS_SEG = sizeof...(SEG) != 0;
+  static_assert(!HAS_SEG || (sizeof...(SEG) == 1 && QBLK == BA_SEG_TILE),
+                "segment ids: q tiles of the pre-pass's tile size");
   constexpr int SWZ = (D == 128) ? 15 : 7;
   constexpr int SWZ_T = 7;
   constexpr int NT = 512;
@@ -385,8 +430,25 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
   for (int dt = 0; dt < D / 32; ++dt) acc[dt] = (f32x16_t)(0.f);
 
   // causal: q tiles wholly before this workgroup's kv rows are masked
-  const int t0 = causal ? (blockIdx.x * 256) / QBLK : 0;
-  const int nt = (Sq + QBLK - 1) / QBLK;
+  const int t0_shape = causal ? (blockIdx.x * 256) / QBLK : 0;
+  const int nt_shape = (Sq + QBLK - 1) / QBLK;
+  int2 trange = {t0_shape, nt_shape};
+  int kid = 0, wk_min = 0, wk_max = 0;
+  const int32_t* qseg = nullptr;
+  const int2* tmm = nullptr;
+  if constexpr (HAS_SEG) {
+    const ba_seg_args sg = ba_seg_of(seg...);
+    const int2 r = sg.blk_range[(int64_t)b * gridDim.x + blockIdx.x];
+    trange.x = max(trange.x, r.x);
+    trange.y = min(trange.y, r.y);
+    if (trange.x >= trange.y) return;  // workgroup-uniform, no barrier yet
+    kid = sg.kv_seg[b * sg.kv_sb + min(kv_col, Sk - 1)];
+    ba_wave_minmax(kid, wk_min, wk_max);
+    qseg = sg.q_seg + b * sg.q_sb;
+    tmm = sg.tile_mm + (int64_t)b * ((Sq + QBLK - 1) / QBLK);
+  }
+  const int t0 = HAS_SEG ? trange.x : t0_shape;
+  const int nt = HAS_SEG ? trange.y : nt_shape;
 
   // per-lane lse*log2e and delta for both subtiles of a tile (l2[qs] =
   // {lse2, delta}), loaded straight from global — clamped, branchless
@@ -461,7 +523,16 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
     if (has_next)
       issue_loads(last_t ? g + 1 : g, last_t ? t0 : t + 1, qreg, greg, l2n);
 
-    const bool active = !causal || (q0 + QBLK - 1 >= kvb);
+    bool active, seg_mask = false;
+    if constexpr (HAS_SEG) {
+      // segment form: the q tile's (min, max) ids against the wave's kv ids
+      const int2 mm = tmm[t];
+      seg_mask = !(mm.x == mm.y && wk_min == wk_max && mm.x == wk_min);
+      active = (!causal || (q0 + QBLK - 1 >= kvb)) && mm.y >= wk_min &&
+               mm.x <= wk_max;
+    } else {
+      active = !causal || (q0 + QBLK - 1 >= kvb);
+    }
     if (active) {
       const float2* ld2s = l2c;  // this tile's lse2/delta (prefetched)
 #pragma unroll
@@ -512,8 +583,10 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
         for (int r = 0; r < 16; ++r) {
           const int q_loc = qs * 32 + ba_crow(r, 0) + 4 * hi;
           const int q_g = q0 + q_loc;
-          const bool valid =
+          bool valid =
               q_g < Sq && kv_col < Sk && (!causal || q_g >= kv_col);
+          if constexpr (HAS_SEG)
+            valid = valid && (!seg_mask || qseg[min(q_g, Sq - 1)] == kid);
           const float e = valid ? st[r] * c2 : BA_NEG_BIG;
           const float p = ba_exp2(e);
           // MODE_DV: P; MODE_DK: dS
@@ -1024,14 +1097,16 @@ static_assert(
         sizeof(bwd_dq_args) == kernarg_size<bwd_dq_kernel_t>::value,
     "bwd_dq_args must mirror bwd_dq_kernel's and bwd_dkv_kernel's parameters");
 
-template <typename T, typename K>
+// `seg`: nothing, or the ba_seg_args of a segment-form kernel
+template <typename T, typename K, typename... SEG>
 static void launch_acc(K kernel, dim3 grid, const bwd_dq_args& a,
-                       hipStream_t stream) {
+                       hipStream_t stream, SEG... seg) {
   kernel<<<grid, 512, 0, stream>>>(
       (const T*)a.dout, (const T*)a.q, (const T*)a.k, (const T*)a.v, a.delta,
       a.lse, a.out, a.Sq, a.Sk, a.N, a.G, a.g_sb, a.g_ss, a.g_sh, a.q_sb,
       a.q_ss, a.q_sh, a.k_sb, a.k_ss, a.k_sh, a.v_sb, a.v_ss, a.v_sh, a.d_sb,
-      a.d_sh, a.l_sb, a.l_sh, a.o_sb, a.o_ss, a.o_sh, a.scale, a.causal);
+      a.d_sh, a.l_sb, a.l_sh, a.o_sb, a.o_ss, a.o_sh, a.scale, a.causal,
+      seg...);
 }
 
 template <typename T, int D, int DQP>
@@ -1048,6 +1123,27 @@ static void launch_dkv(const bwd_dkv_args& a, int64_t B, hipStream_t stream) {
   launch_acc<T>(a.G > 1 ? bwd_dkv_kernel<T, D, MODE, 64, 1>
                         : bwd_dkv_kernel<T, D, MODE, 64, 0>,
                 grid, a, stream);
+}
+
+// the segment forms of the default plan's three kernels; the two sides'
+// pre-pass regions differ (dq owns q rows, dK/dV own kv rows)
+template <typename T, int D>
+static void launch_dq_seg(const bwd_dq_args& a, const ba_seg_args& sg,
+                          int64_t B, hipStream_t stream) {
+  const dim3 grid((unsigned)((a.Sq + 255) / 256), (unsigned)a.N, (unsigned)B);
+  launch_acc<T>(bwd_dq_kernel<T, D, 0, ba_seg_args>, grid, a, stream, sg);
+}
+template <typename T, int D, int MODE>
+static void launch_dkv_seg(const bwd_dkv_args& a, const ba_seg_args& sg,
+                           int64_t B, hipStream_t stream) {
+  const dim3 grid((unsigned)((a.Sk + 255) / 256), (unsigned)(a.N / a.G),
+                  (unsigned)B);
+  if (a.G > 1)
+    launch_acc<T>(bwd_dkv_kernel<T, D, MODE, 64, 1, ba_seg_args>, grid, a,
+                  stream, sg);
+  else
+    launch_acc<T>(bwd_dkv_kernel<T, D, MODE, 64, 0, ba_seg_args>, grid, a,
+                  stream, sg);
 }
 
 struct bwd_dkq_args {
@@ -1078,14 +1174,24 @@ static void launch_dkq(const bwd_dkq_args& a, int64_t B, hipStream_t stream) {
       a.dk_sh, a.dv_sb, a.dv_ss, a.dv_sh, a.scale, a.causal);
 }
 
-extern "C" int bahip_attn_bwd_gqa(
+// what bahip_attn_bwd_seg adds to the plain call
+struct bwd_seg_call {
+  const int32_t *q_seg, *kv_seg;
+  int64_t q_sb, kv_sb;
+  void* ws;
+  int64_t ws_bytes;
+};
+
+// Shared body of the backward entry points; seg null = the plain call.
+static int bwd_entry(
     const void* dout, const void* q, const void* k, const void* v,
     const float* delta, const float* lse, float* dq, float* dk, float* dv,
     int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
     const int64_t gs[3], const int64_t qs[3], const int64_t ks[3],
     const int64_t vs[3], const int64_t ds[2], const int64_t ls[2],
     const int64_t dqs[3], const int64_t dks[3], const int64_t dvs[3],
-    float scale, int causal, int deterministic, int dtype, void* stream) {
+    float scale, int causal, int deterministic, int dtype, void* stream,
+    const bwd_seg_call* seg) {
   (void)deterministic;  // only atomic6 is not deterministic by construction
   if (causal && Sq != Sk)
     return ba_fail(BAHIP_ERR_CAUSAL_SHAPE,
@@ -1121,6 +1227,49 @@ extern "C" int bahip_attn_bwd_gqa(
   };
   const bwd_dq_args dqa = acc_into(dq, dqs);
   const bwd_dkv_args dva = acc_into(dv, dvs), dka = acc_into(dk, dks);
+  if (seg) {
+    // the default plan's kernels in their segment form, after the pre-pass
+    // of both side pairs, all on `stream`
+    const ba_seg_verdict sv = ba_seg_bwd_support(kn);
+    if (sv.knob)
+      return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                     "%s=%d does not support segment ids (default backward "
+                     "plan only)",
+                     sv.knob, sv.value);
+    if (B < 1 || B > 65535 || Sq < 1 || Sk < 1)
+      return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                     "segment ids: unsupported shape B=%d Sq=%d Sk=%d", (int)B,
+                     (int)Sq, (int)Sk);
+    if (!seg->ws || seg->ws_bytes < ba_seg_ws_bytes(B, Sq, Sk))
+      return ba_fail(BAHIP_ERR_WORKSPACE,
+                     "segment workspace of %lld bytes is smaller than the "
+                     "%lld needed",
+                     (long long)(seg->ws ? seg->ws_bytes : 0),
+                     (long long)ba_seg_ws_bytes(B, Sq, Sk));
+    const ba_seg_ws_layout w = ba_seg_ws(B, Sq, Sk);
+    int32_t* ws = (int32_t*)seg->ws;
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = bahip_attn_seg_prepass(seg->q_seg, seg->kv_seg, seg->q_sb,
+                                        seg->kv_sb, B, Sq, Sk, seg->ws,
+                                        seg->ws_bytes, stream))
+      return rc;
+    const ba_seg_args own_q = {seg->q_seg, seg->kv_seg, seg->q_sb, seg->kv_sb,
+                               (const int2*)(ws + w.kv_tile_mm),
+                               (const int2*)(ws + w.q_blk_range)};
+    const ba_seg_args own_kv = {seg->q_seg, seg->kv_seg, seg->q_sb, seg->kv_sb,
+                                (const int2*)(ws + w.q_tile_mm),
+                                (const int2*)(ws + w.kv_blk_range)};
+    return ba_dispatch_td(D, dtype, [&](auto td) {
+      using T = typename decltype(td)::type;
+      constexpr int TD = decltype(td)::D;
+      launch_dq_seg<T, TD>(dqa, own_q, B, st);
+      BA_CHECK_LAUNCH();
+      launch_dkv_seg<T, TD, 0>(dva, own_kv, B, st);
+      BA_CHECK_LAUNCH();
+      launch_dkv_seg<T, TD, 1>(dka, own_kv, B, st);
+      return ba_launch_status();
+    });
+  }
   const bwd_dkq_args dkqa = {
       dout, q, k, v, delta, lse, dq, dk, dv, iSq, iSk, iN,
       gs[0], gs[1], gs[2], qs[0], qs[1], qs[2], ks[0], ks[1], ks[2],
@@ -1147,6 +1296,42 @@ extern "C" int bahip_attn_bwd_gqa(
     }
     return 0;
   });
+}
+
+extern "C" int bahip_attn_bwd_gqa(
+    const void* dout, const void* q, const void* k, const void* v,
+    const float* delta, const float* lse, float* dq, float* dk, float* dv,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t gs[3], const int64_t qs[3], const int64_t ks[3],
+    const int64_t vs[3], const int64_t ds[2], const int64_t ls[2],
+    const int64_t dqs[3], const int64_t dks[3], const int64_t dvs[3],
+    float scale, int causal, int deterministic, int dtype, void* stream) {
+  return bwd_entry(dout, q, k, v, delta, lse, dq, dk, dv, B, Sq, Sk, N, Nk, D,
+                   gs, qs, ks, vs, ds, ls, dqs, dks, dvs, scale, causal,
+                   deterministic, dtype, stream, nullptr);
+}
+
+extern "C" int bahip_attn_bwd_seg(
+    const void* dout, const void* q, const void* k, const void* v,
+    const float* delta, const float* lse, float* dq, float* dk, float* dv,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t gs[3], const int64_t qs[3], const int64_t ks[3],
+    const int64_t vs[3], const int64_t ds[2], const int64_t ls[2],
+    const int64_t dqs[3], const int64_t dks[3], const int64_t dvs[3],
+    float scale, int causal, int deterministic, int dtype,
+    const int32_t* q_seg, const int32_t* kv_seg, int64_t q_seg_stride,
+    int64_t kv_seg_stride, void* seg_workspace, int64_t seg_workspace_bytes,
+    void* stream) {
+  if ((q_seg == nullptr) != (kv_seg == nullptr))
+    return ba_fail(BAHIP_ERR_SEGMENT_IDS,
+                   "segment ids: q_seg and kv_seg must both be given or both "
+                   "be null (%s is null)",
+                   q_seg ? "kv_seg" : "q_seg");
+  const bwd_seg_call sc = {q_seg, kv_seg, q_seg_stride, kv_seg_stride,
+                           seg_workspace, seg_workspace_bytes};
+  return bwd_entry(dout, q, k, v, delta, lse, dq, dk, dv, B, Sq, Sk, N, Nk, D,
+                   gs, qs, ks, vs, ds, ls, dqs, dks, dvs, scale, causal,
+                   deterministic, dtype, stream, q_seg ? &sc : nullptr);
 }
 
 // the equal-heads symbol: Nk = N

@@ -128,6 +128,40 @@ __device__ __forceinline__ void ba_half_pair(float x, float& lo, float& hi) {
   hi = __builtin_bit_cast(float, (int)r[1]);
 }
 
+// ---- segment ids (packed sequences) -----------------------------------
+// The segment form of a kernel takes one ba_seg_args after its last
+// parameter (a trailing parameter pack that is empty in the plain form, so
+// the plain kernels keep their parameter list and their code).  Pair
+// (q row i, kv row j) is visible iff q_seg[i] == kv_seg[j], on top of the
+// kernel's own range and causal rule.  tile_mm and blk_range come from the
+// pre-pass (ba_seg_prepass, attn_fwd.hip): "streamed" is the side the
+// kernel walks in 64-row tiles (kv for the forward and dq, q for dK/dV),
+// "block" the 256 rows a workgroup owns.
+struct ba_seg_args {
+  const int32_t* q_seg;   // [B, Sq], seq stride 1
+  const int32_t* kv_seg;  // [B, Sk], seq stride 1
+  int64_t q_sb, kv_sb;    // batch strides in elements
+  const int2* tile_mm;    // [B][streamed tiles]: (min, max) id of the tile
+  const int2* blk_range;  // [B][gridDim.x]: [lo, hi) streamed tiles that
+                          // can hold an id of the block; lo >= hi = none
+};
+__device__ __forceinline__ ba_seg_args ba_seg_of() { return {}; }
+__device__ __forceinline__ ba_seg_args ba_seg_of(const ba_seg_args& s) {
+  return s;
+}
+
+// min and max of x over the wave, as wave-uniform (scalar) values
+__device__ __forceinline__ void ba_wave_minmax(int x, int& mn, int& mx) {
+  mn = mx = x;
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+    mn = min(mn, __shfl_xor(mn, o));
+    mx = max(mx, __shfl_xor(mx, o));
+  }
+  mn = __builtin_amdgcn_readfirstlane(mn);
+  mx = __builtin_amdgcn_readfirstlane(mx);
+}
+
 // 16-value max via 3-input nesting (clang fuses fmaxf chains to v_max3)
 __device__ __forceinline__ float ba_max16(const f32x16_t& v) {
   float a = fmaxf(fmaxf(v[0], v[1]), v[2]);

@@ -28,6 +28,7 @@
 #include "attn_host.h"
 #include "fwd_variants.h"
 #include "gqa_heads.h"
+#include "seg_support.h"
 #include "vt_image.h"
 
 #include <stddef.h>
@@ -97,8 +98,16 @@ __device__ __forceinline__ int ba_buf_of(ba_dyn d) { return d.value; }
 // attn_vt_image_kernel: `v` points at the image, v_sb / v_sh are its batch
 // and head strides, v_ss is unused, and a tile's staging is PT 16-byte
 // copies like K's.  Default variant <0,1,512,2,0> only.
+// SEG: empty = the plain kernel.  One ba_seg_args = the segment-id form
+// (attn_common.h): the id equality joins the boundary mask; the tile loop
+// covers only the block's [lo, hi) range from the pre-pass; a wave skips a
+// tile whose (min, max) ids miss those of its rows; masked entries get
+// weight exactly 0, so a row that sees no key ends with l = 0; a workgroup
+// with an empty range leaves before its first barrier.  Default variant
+// with VSRC=0 only.
 template <typename T, int D, int KVBLK, int OUT_STATE, int VPATH, int SUBT,
-          int NT = 512, int NBUF = 2, int KREG = 0, int VSRC = 0>
+          int NT = 512, int NBUF = 2, int KREG = 0, int VSRC = 0,
+          typename... SEG>
 __global__ __launch_bounds__(NT) void attn_fwd_kernel(
     const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
     float* __restrict__ o, float* __restrict__ lse,
@@ -111,9 +120,13 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
     float* __restrict__ st_acc, float* __restrict__ st_m,
     float* __restrict__ st_l,
     int64_t a_sb, int64_t a_ss, int64_t a_sh,
-    int64_t ml_sb, int64_t ml_sh, int carry_in) {
+    int64_t ml_sb, int64_t ml_sh, int carry_in, SEG... seg) {
   using MT = mfma_traits<T>;
   using frag = typename MT::frag;
+  constexpr bool HAS_SEG = sizeof...(SEG) != 0;
+  static_assert(!HAS_SEG || (sizeof...(SEG) == 1 && VPATH == 0 && SUBT == 1 &&
+                             NT == 512 && NBUF == 2 && KREG == 0 && VSRC == 0),
+                "segment ids: the default variant, V transposed in-kernel");
   constexpr int SWZ_K = (D == 128) ? 15 : 7;  // K image rows are 2*D bytes
   constexpr int SWZ_V = 7;                    // V^T image rows are 128 bytes
   constexpr int PT = (KVBLK * D / 8) / NT;
@@ -192,7 +205,49 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
 
   const int kv_limit =
       causal ? min(Sk, (int)(blockIdx.x + 1) * QROWS) : Sk;
-  const int nt = (kv_limit + KVBLK - 1) / KVBLK;
+  const int nt_shape = (kv_limit + KVBLK - 1) / KVBLK;
+  int2 trange = {0, nt_shape};
+  // segment form: this lane's q id, the wave's (min, max) of them, the kv
+  // ids and tile summaries of this batch row, and the block's tile range
+  int qid = 0, wq_min = 0, wq_max = 0;
+  const int32_t* kseg = nullptr;
+  const int2* tmm = nullptr;
+  bool seg_mask = false;  // the current tile needs the id compare
+  if constexpr (HAS_SEG) {
+    const ba_seg_args sg = ba_seg_of(seg...);
+    const int2 r = sg.blk_range[(int64_t)b * gridDim.x + blockIdx.x];
+    trange.x = r.x;
+    trange.y = min(trange.y, r.y);
+    if (trange.x >= trange.y) {
+      // nothing visible to any row of this workgroup (uniform: no barrier
+      // has been reached): o = 0, lse = -inf / a fresh empty state / the
+      // carried state as it is
+      if (q_row < Sq && !(OUT_STATE && carry_in)) {
+        float* row = OUT_STATE
+                         ? st_acc + b * a_sb + (int64_t)q_row * a_ss + n * a_sh
+                         : o + (((int64_t)b * Sq + q_row) * N + n) * D;
+#pragma unroll
+        for (int dt = 0; dt < D / 32; ++dt)
+#pragma unroll
+          for (int r2 = 0; r2 < 16; ++r2) row[dt * 32 + ba_crow(r2, hi)] = 0.f;
+        if (hi == 0) {
+          if (OUT_STATE) {
+            st_m[b * ml_sb + n * ml_sh + q_row] = BA_NEG_BIG;
+            st_l[b * ml_sb + n * ml_sh + q_row] = 0.f;
+          } else {
+            lse[((int64_t)b * N + n) * Sq + q_row] = -__builtin_inff();
+          }
+        }
+      }
+      return;
+    }
+    qid = sg.q_seg[b * sg.q_sb + min(q_row, Sq - 1)];
+    ba_wave_minmax(qid, wq_min, wq_max);
+    kseg = sg.kv_seg + b * sg.kv_sb;
+    tmm = sg.tile_mm + (int64_t)b * ((Sk + KVBLK - 1) / KVBLK);
+  }
+  const int t_first = HAS_SEG ? trange.x : 0;
+  const int nt = HAS_SEG ? trange.y : nt_shape;
   static_assert(SUBT != 2 || (NBUF == 4 && VPATH == 0),
                 "the T15 pipeline needs NBUF=4 and the V^T image");
   static_assert(SUBT != 3 || (NBUF == 4 && VPATH == 0 && NT == 256),
@@ -239,6 +294,9 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
     for (int r = 0; r < 16; ++r) {
       const int kv_g = base + off + ba_crow(r, 0) + 4 * hi;
       if (!(kv_g < Sk && (!causal || kv_g <= q_row))) s[r] = BA_NEG_BIG;
+      if constexpr (HAS_SEG) {
+        if (seg_mask && kseg[min(kv_g, Sk - 1)] != qid) s[r] = BA_NEG_BIG;
+      }
     }
   };
   // row max in the exp2 domain.  The softmax scale is folded into the exp
@@ -281,7 +339,15 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
     float rowsum = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      s[r] = ba_exp2(__builtin_fmaf(s[r], c2, -m2));
+      // segment form: a masked entry weighs exactly 0 even while the row's
+      // running max is still at the masked level (a row whose tiles so far
+      // held no visible key), where the exponent below would not be small
+      if constexpr (HAS_SEG) {
+        const bool masked = s[r] == BA_NEG_BIG;
+        s[r] = masked ? 0.f : ba_exp2(__builtin_fmaf(s[r], c2, -m2));
+      } else {
+        s[r] = ba_exp2(__builtin_fmaf(s[r], c2, -m2));
+      }
       rowsum += s[r];
     }
     if (HSWAP) {
@@ -490,7 +556,7 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
   frag kfr[KREG == 1 ? 2 : 1][D / 16];  // KREG: resident K fragments
   {  // prologue: tiles 0..NBUF-2
     u32x4_t kreg[PT], vreg[PT];
-    issue_loads(0, kreg, vreg);
+    issue_loads(t_first, kreg, vreg);
     write_lds(0, kreg, vreg);
     if (KREG == 1) {
       load_k_sub(0, 0, kfr[0]);
@@ -522,14 +588,26 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
     u32x4_t kreg[PT], vreg[PT];
     if (has_next) issue_loads(t + AHEAD, kreg, vreg);
 
-    const bool active = !causal || (kv0 <= qb + 31);
+    bool active, full;
+    if constexpr (HAS_SEG) {
+      // segment form: the tile's (min, max) ids against the wave's; a full
+      // tile also has one id on both sides
+      const int2 mm = tmm[t];
+      seg_mask = !(mm.x == mm.y && wq_min == wq_max && mm.x == wq_min);
+      active = (!causal || (kv0 <= qb + 31)) && mm.y >= wq_min &&
+               mm.x <= wq_max;
+      full = (kv0 + KVBLK <= Sk) && (!causal || (kv0 + KVBLK - 1 <= qb)) &&
+             !seg_mask;
+    } else {
+      active = !causal || (kv0 <= qb + 31);
+    }
     if (active) {
       // a full tile needs no mask: inside Sk and, if causal, at or below
       // the diagonal for every q row of this wave.  (SUBT=0 takes its own
       // copy after its QK MFMAs: reading this one costs its register-tight
       // tr16 kernels 4 to 8 bytes more scratch.)
-      const bool full =
-          (kv0 + KVBLK <= Sk) && (!causal || (kv0 + KVBLK - 1 <= qb));
+      if constexpr (!HAS_SEG)
+        full = (kv0 + KVBLK <= Sk) && (!causal || (kv0 + KVBLK - 1 <= qb));
       if (SUBT == 3) {
         // NOTE: a C-level warmup peel (separate guarded/steady calls)
         // measured -48% — four inlined phase copies bloat the loop body.
@@ -670,7 +748,9 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
     // (profiles/fwd_vt/README.md): what matters is that the placement is
     // a measured one and stays put, which this directive provides.
     asm volatile(".p2align 7");
-    for (int tb = 0; tb < nt; tb += NBUF) {
+    // (segment form: the range may start at any tile; the buffer of a copy
+    // is its position in the unrolled body, not the tile's parity)
+    for (int tb = t_first; tb < nt; tb += NBUF) {
       [[clang::always_inline]] tile_body(tb, ba_ic<0>{});
       if (tb + 1 < nt) [[clang::always_inline]] tile_body(tb + 1, ba_ic<1 % NBUF>{});
       if (NBUF > 2) {
@@ -705,7 +785,9 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
         st_l[b * ml_sb + n * ml_sh + q_row] = lsum;
       }
     } else {
-      const float inv_l = 1.f / lsum;
+      // segment form: a row that saw no key has l = 0: o = 0, lse = -inf
+      float inv_l = 1.f / lsum;
+      if constexpr (HAS_SEG) inv_l = lsum == 0.f ? 0.f : inv_l;
       float* orow = o + (((int64_t)b * Sq + q_row) * N + n) * D;
 #pragma unroll
       for (int dt = 0; dt < D / 32; ++dt)
@@ -735,7 +817,9 @@ __global__ void attn_fwd_finalize_kernel(
   const int n = blockIdx.y, b = blockIdx.z;
   if (s >= S) return;
   const float lv = l[((int64_t)b * N + n) * S + s];
-  const float inv_l = 1.f / lv;
+  // l == 0: a row that saw no key in any round (possible with segment ids
+  // in direct tile calls only): o = 0, and lse below comes out -inf
+  const float inv_l = lv > 0.f ? 1.f / lv : 0.f;
   const float* arow = acc + (((int64_t)b * S + s) * N + n) * D + sub * 16;
   T* orow = o + (((int64_t)b * S + s) * N + n) * D + sub * 16;
 #pragma unroll
@@ -785,7 +869,104 @@ __global__ __launch_bounds__(256) void attn_vt_image_kernel(
   }
 }
 
+// ---- segment-id pre-pass (layout: seg_support.h) ------------------------
+// Step 1, one wave per 64-row tile of the streamed side: the tile's
+// (min, max) id, and a per-batch-row flag raised where an id is smaller
+// than its predecessor.  Rows past S repeat the last id.
+__global__ __launch_bounds__(256) void seg_tile_minmax_kernel(
+    const int32_t* __restrict__ ids, int64_t sb, int S, int ntiles,
+    int2* __restrict__ mm, int* __restrict__ nonmono) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
+  if (t >= ntiles) return;
+  const int i = min(t * BA_SEG_TILE + lane, S - 1);
+  const int32_t* row = ids + b * sb;
+  const int id = row[i];
+  if (__any(row[max(i - 1, 0)] > id) && lane == 0) atomicOr(nonmono + b, 1);
+  int mn, mx;
+  ba_wave_minmax(id, mn, mx);
+  if (lane == 0) mm[(int64_t)b * ntiles + t] = make_int2(mn, mx);
+}
+
+// Step 2, one workgroup per 256-row block of the owning side: the range
+// [lo, hi) of streamed tiles whose (min, max) overlaps the block's.  Where
+// the streamed ids are non-decreasing (packed documents, in every layout
+// of the ring) the tile summaries are sorted and one thread finds the range
+// by two binary searches; for one non-decreasing id sequence on both sides
+// (a packed sequence attending itself) these are exactly the tiles that
+// share an id with the block.  Otherwise the workgroup scans the summaries and the range is the hull of
+// the overlapping tiles: conservative, still correct under the element
+// mask.
+__global__ __launch_bounds__(256) void seg_block_range_kernel(
+    const int32_t* __restrict__ ids, int64_t sb, int S,
+    const int2* __restrict__ mm, int ntiles, const int* __restrict__ nonmono,
+    int2* __restrict__ range) {
+  __shared__ int s_min, s_max, s_lo, s_hi;
+  const int tid = threadIdx.x, b = blockIdx.y;
+  if (tid == 0) {
+    s_min = INT32_MAX;
+    s_max = INT32_MIN;
+    s_lo = ntiles;
+    s_hi = 0;
+  }
+  __syncthreads();
+  int mn, mx;
+  ba_wave_minmax(ids[b * sb + min((int)blockIdx.x * BA_SEG_BLOCK + tid, S - 1)],
+                 mn, mx);
+  if ((tid & 63) == 0) {
+    atomicMin(&s_min, mn);
+    atomicMax(&s_max, mx);
+  }
+  __syncthreads();
+  const int bmin = s_min, bmax = s_max;
+  const int2* m = mm + (int64_t)b * ntiles;
+  int2* out = range + (int64_t)b * gridDim.x + blockIdx.x;
+  if (!nonmono[b]) {
+    if (tid == 0) {
+      int lo = 0, hi = ntiles;  // first tile with max >= bmin
+      while (lo < hi) {
+        const int mid = (lo + hi) / 2;
+        if (m[mid].y >= bmin) hi = mid; else lo = mid + 1;
+      }
+      int lo2 = lo, hi2 = ntiles;  // first tile with min > bmax
+      while (lo2 < hi2) {
+        const int mid = (lo2 + hi2) / 2;
+        if (m[mid].x > bmax) hi2 = mid; else lo2 = mid + 1;
+      }
+      *out = make_int2(lo, lo2);
+    }
+    return;
+  }
+  for (int t = tid; t < ntiles; t += 256)
+    if (m[t].y >= bmin && m[t].x <= bmax) {
+      atomicMin(&s_lo, t);
+      atomicMax(&s_hi, t + 1);
+    }
+  __syncthreads();
+  if (tid == 0) *out = make_int2(s_lo, s_hi);
+}
+
 }  // namespace
+
+// ranges of one side pair: `own` is the side whose 256-row blocks the
+// kernel's workgroups hold, `str` the side they stream in 64-row tiles
+int ba_seg_prepass(const int32_t* own, int64_t own_sb, int64_t S_own,
+                   const int32_t* str, int64_t str_sb, int64_t S_str,
+                   int64_t B, int32_t* flags, int32_t* tile_mm,
+                   int32_t* blk_range, hipStream_t stream) {
+  const int nt = (int)ba_seg_tiles(S_str), nb = (int)ba_seg_blocks(S_own);
+  hipError_t e = hipMemsetAsync(flags, 0, (size_t)B * sizeof(int32_t), stream);
+  if (e != hipSuccess)
+    return ba_fail((int)e, "segment pre-pass memset failed: %s",
+                   hipGetErrorString(e));
+  seg_tile_minmax_kernel<<<dim3((unsigned)((nt + 3) / 4), (unsigned)B), 256, 0,
+                           stream>>>(str, str_sb, (int)S_str, nt,
+                                     (int2*)tile_mm, flags);
+  seg_block_range_kernel<<<dim3((unsigned)nb, (unsigned)B), 256, 0, stream>>>(
+      own, own_sb, (int)S_own, (const int2*)tile_mm, nt, flags,
+      (int2*)blk_range);
+  return ba_launch_status();
+}
 
 extern "C" const char* bahip_last_error(void) { return ba_g_err; }
 
@@ -830,6 +1011,91 @@ static void launch_fwd(const fwd_args& a, int64_t B, hipStream_t stream) {
           a.N, a.G, a.q_sb, a.q_ss, a.q_sh, a.k_sb, a.k_ss, a.k_sh, a.v_sb, a.v_ss,
           a.v_sh, a.scale, a.causal, a.st_acc, a.st_m, a.st_l, a.a_sb, a.a_ss,
           a.a_sh, a.ml_sb, a.ml_sh, a.carry_in);
+}
+
+// ---- segment-id form ----------------------------------------------------
+// What a *_seg entry point adds to the plain call.
+struct fwd_seg_call {
+  const int32_t *q_seg, *kv_seg;
+  int64_t q_sb, kv_sb;
+  void* ws;
+  int64_t ws_bytes;
+};
+
+// One of the two id pointers without the other is an error; both null is
+// the plain call (0), both given the segment form (1).
+static int seg_ids_given(const void* q_seg, const void* kv_seg, int* given) {
+  if ((q_seg == nullptr) != (kv_seg == nullptr))
+    return ba_fail(BAHIP_ERR_SEGMENT_IDS,
+                   "segment ids: q_seg and kv_seg must both be given or both "
+                   "be null (%s is null)",
+                   q_seg ? "kv_seg" : "q_seg");
+  *given = q_seg != nullptr;
+  return 0;
+}
+
+// The forward with ids: the default variant only, V transposed in the
+// kernel whatever BA_FWD_VT says (one kernel, so the results cannot depend
+// on that knob), never the module kernel.  Pre-pass, then the forward, on
+// the same stream.
+static int fwd_seg_entry(const fwd_args& a, const fwd_seg_call& sc,
+                         int out_state, int64_t B, int64_t Sq, int64_t Sk,
+                         int64_t D, int dtype, hipStream_t stream) {
+  ba_fwd_knobs kn;
+  kn.vpath = ba_env_int(BA_FWD_KNOB_SPECS[0].env, kn.vpath);
+  kn.subt = ba_env_int(BA_FWD_KNOB_SPECS[1].env, kn.subt);
+  kn.nt = ba_env_int(BA_FWD_KNOB_SPECS[2].env, kn.nt);
+  kn.nbuf = ba_env_int(BA_FWD_KNOB_SPECS[3].env, kn.nbuf);
+  kn.kreg = ba_env_int(BA_FWD_KNOB_SPECS[4].env, kn.kreg);
+  const ba_fwd_choice c = ba_fwd_select(kn);
+  if (c.bad_knob)
+    return ba_fail(BAHIP_ERR_BAD_KNOB, "%s=%d is not an accepted value",
+                   c.bad_knob, c.bad_value);
+  const ba_seg_verdict sv = ba_seg_fwd_support(kn);
+  if (sv.knob)
+    return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                   "%s=%d does not support segment ids (default forward "
+                   "variant only)",
+                   sv.knob, sv.value);
+  if (B < 1 || B > 65535 || Sq < 1 || Sk < 1)
+    return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                   "segment ids: unsupported shape B=%d Sq=%d Sk=%d", (int)B,
+                   (int)Sq, (int)Sk);
+  if (!sc.ws || sc.ws_bytes < ba_seg_ws_bytes(B, Sq, Sk))
+    return ba_fail(BAHIP_ERR_WORKSPACE,
+                   "segment workspace of %lld bytes is smaller than the %lld "
+                   "needed",
+                   (long long)(sc.ws ? sc.ws_bytes : 0),
+                   (long long)ba_seg_ws_bytes(B, Sq, Sk));
+  const ba_seg_ws_layout w = ba_seg_ws(B, Sq, Sk);
+  int32_t* ws = (int32_t*)sc.ws;
+  if (int rc = ba_seg_prepass(sc.q_seg, sc.q_sb, Sq, sc.kv_seg, sc.kv_sb, Sk,
+                              B, ws + w.flags_kv, ws + w.kv_tile_mm,
+                              ws + w.q_blk_range, stream))
+    return rc;
+  const ba_seg_args sg = {sc.q_seg, sc.kv_seg, sc.q_sb, sc.kv_sb,
+                          (const int2*)(ws + w.kv_tile_mm),
+                          (const int2*)(ws + w.q_blk_range)};
+  return ba_dispatch_td(D, dtype, [&](auto td) {
+    using T = typename decltype(td)::type;
+    constexpr int TD = decltype(td)::D;
+    constexpr ba_fwd_variant P = BA_FWD_PRODUCTION;
+    const dim3 grid = fwd_grid(a, B, P.nt);
+    auto go = [&](auto kernel) {
+      kernel<<<grid, dim3(P.nt), 0, stream>>>(
+          (const T*)a.q, (const T*)a.k, (const T*)a.v, a.o, a.lse, a.Sq, a.Sk,
+          a.N, a.G, a.q_sb, a.q_ss, a.q_sh, a.k_sb, a.k_ss, a.k_sh, a.v_sb,
+          a.v_ss, a.v_sh, a.scale, a.causal, a.st_acc, a.st_m, a.st_l, a.a_sb,
+          a.a_ss, a.a_sh, a.ml_sb, a.ml_sh, a.carry_in, sg);
+    };
+    if (out_state)
+      go(attn_fwd_kernel<T, TD, 64, 1, P.vpath, P.subt, P.nt, P.nbuf, P.kreg,
+                         0, ba_seg_args>);
+    else
+      go(attn_fwd_kernel<T, TD, 64, 0, P.vpath, P.subt, P.nt, P.nbuf, P.kreg,
+                         0, ba_seg_args>);
+    return ba_launch_status();
+  });
 }
 
 // The per-call knobs: the variant the BA_FWD_* table selects, and whether
@@ -898,7 +1164,8 @@ static int fwd_entry(void* hip_function, int out_state, const void* q,
                      const int64_t* vs, float scale, int causal, int dtype,
                      float* acc, float* m,
                      float* l, const int64_t* as, const int64_t* mls,
-                     int carry_in, void* ws, int64_t ws_bytes, void* stream) {
+                     int carry_in, void* ws, int64_t ws_bytes, void* stream,
+                     const fwd_seg_call* seg = nullptr) {
   if (causal && Sq != Sk)
     return ba_fail(BAHIP_ERR_CAUSAL_SHAPE,
                    "causal tiles require Sq == Sk (%d vs %d)", (int)Sq,
@@ -915,6 +1182,9 @@ static int fwd_entry(void* hip_function, int out_state, const void* q,
                       qs[0], qs[1], qs[2], ks[0], ks[1], ks[2],
                       vs[0], vs[1], vs[2], scale, causal, acc, m, l,
                       as[0], as[1], as[2], mls[0], mls[1], carry_in};
+  if (seg)
+    return fwd_seg_entry(a, *seg, out_state, B, Sq, Sk, D, dtype,
+                         (hipStream_t)stream);
   if (hip_function) {
     if (D != 128 || (dtype != BAHIP_F16 && dtype != BAHIP_BF16))
       return ba_fail(BAHIP_ERR_UNSUPPORTED,
@@ -1009,6 +1279,79 @@ extern "C" int bahip_attn_fwd_accum_gqa_ws(
                    Nk, D, q_strides, k_strides, v_strides, softmax_scale,
                    causal, dtype, acc, m, l, acc_strides, ml_strides, carry_in,
                    workspace, workspace_bytes, stream);
+}
+
+extern "C" int bahip_attn_fwd_seg(
+    const void* q, const void* k, const void* v, float* o, float* lse,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    void* workspace, int64_t workspace_bytes, const int32_t* q_seg,
+    const int32_t* kv_seg, int64_t q_seg_stride, int64_t kv_seg_stride,
+    void* seg_workspace, int64_t seg_workspace_bytes, void* stream) {
+  int given;
+  if (int rc = seg_ids_given(q_seg, kv_seg, &given)) return rc;
+  const fwd_seg_call sc = {q_seg, kv_seg, q_seg_stride, kv_seg_stride,
+                           seg_workspace, seg_workspace_bytes};
+  return fwd_entry(nullptr, 0, q, k, v, o, lse, B, Sq, Sk, N, Nk, D, q_strides,
+                   k_strides, v_strides, softmax_scale, causal, dtype, nullptr,
+                   nullptr, nullptr, nullptr, nullptr, 0, workspace,
+                   workspace_bytes, stream, given ? &sc : nullptr);
+}
+
+extern "C" int bahip_attn_fwd_accum_seg(
+    void* hip_function, const void* q, const void* k, const void* v,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    float* acc, float* m, float* l, const int64_t acc_strides[3],
+    const int64_t ml_strides[2], int carry_in, void* workspace,
+    int64_t workspace_bytes, const int32_t* q_seg, const int32_t* kv_seg,
+    int64_t q_seg_stride, int64_t kv_seg_stride, void* seg_workspace,
+    int64_t seg_workspace_bytes, void* stream) {
+  int given;
+  if (int rc = seg_ids_given(q_seg, kv_seg, &given)) return rc;
+  const fwd_seg_call sc = {q_seg, kv_seg, q_seg_stride, kv_seg_stride,
+                           seg_workspace, seg_workspace_bytes};
+  return fwd_entry(hip_function, 1, q, k, v, nullptr, nullptr, B, Sq, Sk, N,
+                   Nk, D, q_strides, k_strides, v_strides, softmax_scale,
+                   causal, dtype, acc, m, l, acc_strides, ml_strides, carry_in,
+                   workspace, workspace_bytes, stream, given ? &sc : nullptr);
+}
+
+extern "C" int64_t bahip_attn_seg_workspace_bytes(int64_t B, int64_t Sq,
+                                                  int64_t Sk) {
+  return ba_seg_ws_bytes(B, Sq, Sk);
+}
+
+extern "C" int bahip_attn_seg_prepass(const int32_t* q_seg,
+                                      const int32_t* kv_seg,
+                                      int64_t q_seg_stride,
+                                      int64_t kv_seg_stride, int64_t B,
+                                      int64_t Sq, int64_t Sk,
+                                      void* seg_workspace,
+                                      int64_t seg_workspace_bytes,
+                                      void* stream) {
+  if (!q_seg || !kv_seg || B < 1 || B > 65535 || Sq < 1 || Sk < 1)
+    return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                   "segment pre-pass: ids null or unsupported shape B=%d "
+                   "Sq=%d Sk=%d",
+                   (int)B, (int)Sq, (int)Sk);
+  if (!seg_workspace || seg_workspace_bytes < ba_seg_ws_bytes(B, Sq, Sk))
+    return ba_fail(BAHIP_ERR_WORKSPACE,
+                   "segment workspace of %lld bytes is smaller than the %lld "
+                   "needed",
+                   (long long)(seg_workspace ? seg_workspace_bytes : 0),
+                   (long long)ba_seg_ws_bytes(B, Sq, Sk));
+  const ba_seg_ws_layout w = ba_seg_ws(B, Sq, Sk);
+  int32_t* ws = (int32_t*)seg_workspace;
+  if (int rc = ba_seg_prepass(q_seg, q_seg_stride, Sq, kv_seg, kv_seg_stride,
+                              Sk, B, ws + w.flags_kv, ws + w.kv_tile_mm,
+                              ws + w.q_blk_range, (hipStream_t)stream))
+    return rc;
+  return ba_seg_prepass(kv_seg, kv_seg_stride, Sk, q_seg, q_seg_stride, Sq, B,
+                        ws + w.flags_q, ws + w.q_tile_mm, ws + w.kv_blk_range,
+                        (hipStream_t)stream);
 }
 
 extern "C" int64_t bahip_attn_vt_image_bytes(int64_t B, int64_t Nk,

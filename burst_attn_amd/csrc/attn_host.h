@@ -48,6 +48,15 @@ inline int ba_launch_status() {
     if (int rc_ = ba_launch_status()) return rc_;  \
   } while (0)
 
+// Segment-id pre-pass (defined in attn_fwd.hip, layout in seg_support.h):
+// tile summaries of the streamed side `str` and, per 256-row block of the
+// owning side `own`, the range of streamed tiles to visit.  The three
+// outputs are the workspace regions of that side pair.
+int ba_seg_prepass(const int32_t* own, int64_t own_sb, int64_t S_own,
+                   const int32_t* str, int64_t str_sb, int64_t S_str,
+                   int64_t B, int32_t* flags, int32_t* tile_mm,
+                   int32_t* blk_range, hipStream_t stream);
+
 // explicit-kernarg segment size of a kernel, from its parameter types
 template <typename F>
 struct kernarg_size;

@@ -81,22 +81,90 @@ at::Tensor fwd_workspace(const at::Tensor& q, const at::Tensor& k) {
   return at::empty({bytes}, q.options().dtype(at::kByte));
 }
 
+// Segment ids of a call: both or neither; int32 [B, Sq] / [B, Sk] with a
+// contiguous seq dim, on q's device.  A given pair comes with the pre-pass
+// workspace, allocated per call on the current stream like the V^T image's.
+struct SegIds {
+  const int32_t *q = nullptr, *kv = nullptr;
+  int64_t q_sb = 0, kv_sb = 0;
+  at::Tensor ws;
+  void* ws_ptr() const { return ws.defined() ? ws.data_ptr() : nullptr; }
+  int64_t ws_bytes() const { return ws.defined() ? ws.numel() : 0; }
+};
+
+void check_seg(const at::Tensor& s, const at::Tensor& q, int64_t rows,
+               const char* name) {
+  TORCH_CHECK(s.scalar_type() == at::kInt, name, " must be int32, got ",
+              s.scalar_type());
+  TORCH_CHECK(s.device() == q.device(), name, " must be on q's device");
+  TORCH_CHECK(s.dim() == 2 && s.size(0) == q.size(0) && s.size(1) == rows,
+              name, " must be [B, S] = [", q.size(0), ", ", rows, "], got ",
+              s.sizes());
+  TORCH_CHECK(s.stride(1) == 1 || rows == 1, name,
+              " seq dim must be contiguous");
+}
+
+SegIds seg_ids(const c10::optional<at::Tensor>& q_seg,
+               const c10::optional<at::Tensor>& kv_seg, const at::Tensor& q,
+               const at::Tensor& k) {
+  SegIds s;
+  TORCH_CHECK(q_seg.has_value() == kv_seg.has_value(),
+              "q_seg and kv_seg must be given together");
+  if (!q_seg.has_value()) return s;
+  check_seg(*q_seg, q, q.size(1), "q_seg");
+  check_seg(*kv_seg, q, k.size(1), "kv_seg");
+  s.q = q_seg->data_ptr<int32_t>();
+  s.kv = kv_seg->data_ptr<int32_t>();
+  s.q_sb = q_seg->stride(0);
+  s.kv_sb = kv_seg->stride(0);
+  s.ws = at::empty(
+      {bahip_attn_seg_workspace_bytes(q.size(0), q.size(1), k.size(1))},
+      q.options().dtype(at::kByte));
+  return s;
+}
+
+// The pre-pass alone on [B, Sq] / [B, Sk] ids: the workspace as int32
+// words (layout: bahip_attn_seg_prepass).  For tests and measurements.
+at::Tensor attn_seg_prepass(const at::Tensor& q_seg, const at::Tensor& kv_seg) {
+  TORCH_CHECK(q_seg.is_cuda() && kv_seg.is_cuda() && q_seg.dim() == 2 &&
+                  kv_seg.dim() == 2 && q_seg.size(0) == kv_seg.size(0) &&
+                  q_seg.scalar_type() == at::kInt &&
+                  kv_seg.scalar_type() == at::kInt &&
+                  (q_seg.stride(1) == 1 || q_seg.size(1) == 1) &&
+                  (kv_seg.stride(1) == 1 || kv_seg.size(1) == 1),
+              "segment ids must be int32 [B, S] GPU tensors, seq contiguous");
+  const auto B = q_seg.size(0), Sq = q_seg.size(1), Sk = kv_seg.size(1);
+  auto ws = at::empty({bahip_attn_seg_workspace_bytes(B, Sq, Sk) / 4},
+                      q_seg.options());
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  BA_CALL(bahip_attn_seg_prepass(q_seg.data_ptr<int32_t>(),
+                                 kv_seg.data_ptr<int32_t>(), q_seg.stride(0),
+                                 kv_seg.stride(0), B, Sq, Sk, ws.data_ptr(),
+                                 ws.numel() * 4, stream));
+  return ws;
+}
+
 std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k,
                                  const at::Tensor& v, double softmax_scale,
-                                 bool causal) {
+                                 bool causal,
+                                 const c10::optional<at::Tensor>& q_seg,
+                                 const c10::optional<at::Tensor>& kv_seg) {
   check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
+  const SegIds seg = seg_ids(q_seg, kv_seg, q, k);
   auto o = at::empty({B, Sq, N, D}, q.options().dtype(at::kFloat));
   auto lse = at::empty({B, N, Sq}, q.options().dtype(at::kFloat));
-  auto ws = fwd_workspace(q, k);
+  // with ids the forward transposes V in the kernel: no image workspace
+  auto ws = seg.q ? at::Tensor() : fwd_workspace(q, k);
   auto stream = at::hip::getCurrentHIPStream().stream();
-  BA_CALL(bahip_attn_fwd_gqa_ws(
+  BA_CALL(bahip_attn_fwd_seg(
       q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr<float>(),
       lse.data_ptr<float>(), B, Sq, Sk, N, k.size(2), D, Strides3(q),
       Strides3(k), Strides3(v), (float)softmax_scale, causal ? 1 : 0,
       dtype_code(q), ws.defined() ? ws.data_ptr() : nullptr,
-      ws.defined() ? ws.numel() : 0, stream));
+      ws.defined() ? ws.numel() : 0, seg.q, seg.kv, seg.q_sb, seg.kv_sb,
+      seg.ws_ptr(), seg.ws_bytes(), stream));
   return {o, lse};
 }
 
@@ -136,10 +204,13 @@ at::Tensor attn_vt_image(const at::Tensor& v, c10::optional<at::Tensor> out) {
 void fwd_accum_call(void* asm_fn, const at::Tensor& q, const at::Tensor& k,
                     const at::Tensor& v, double softmax_scale, bool causal,
                     at::Tensor& acc, at::Tensor& m, at::Tensor& l,
-                    bool carry_in) {
+                    bool carry_in,
+                    const c10::optional<at::Tensor>& q_seg = c10::nullopt,
+                    const c10::optional<at::Tensor>& kv_seg = c10::nullopt) {
   check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
+  const SegIds seg = seg_ids(q_seg, kv_seg, q, k);
   TORCH_CHECK(acc.scalar_type() == at::kFloat && m.scalar_type() == at::kFloat
                   && l.scalar_type() == at::kFloat, "state must be fp32");
   TORCH_CHECK(acc.size(1) == Sq && m.size(2) == Sq && l.size(2) == Sq,
@@ -149,23 +220,27 @@ void fwd_accum_call(void* asm_fn, const at::Tensor& q, const at::Tensor& k,
   int64_t mls[2] = {m.stride(0), m.stride(1)};
   TORCH_CHECK(l.stride(0) == mls[0] && l.stride(1) == mls[1],
               "m/l stride mismatch");
-  // the module kernel transposes V itself: no workspace
-  auto ws = asm_fn ? at::Tensor() : fwd_workspace(q, k);
+  // the module kernel and the segment form transpose V themselves: no
+  // image workspace
+  auto ws = (asm_fn || seg.q) ? at::Tensor() : fwd_workspace(q, k);
   auto stream = at::hip::getCurrentHIPStream().stream();
-  BA_CALL(bahip_attn_fwd_accum_gqa_ws(
+  BA_CALL(bahip_attn_fwd_accum_seg(
       asm_fn, q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Sq, Sk, N,
       k.size(2), D, Strides3(q), Strides3(k), Strides3(v), (float)softmax_scale,
       causal ? 1 : 0, dtype_code(q), acc.data_ptr<float>(),
       m.data_ptr<float>(), l.data_ptr<float>(), Strides3(acc), mls,
       carry_in ? 1 : 0, ws.defined() ? ws.data_ptr() : nullptr,
-      ws.defined() ? ws.numel() : 0, stream));
+      ws.defined() ? ws.numel() : 0, seg.q, seg.kv, seg.q_sb, seg.kv_sb,
+      seg.ws_ptr(), seg.ws_bytes(), stream));
 }
 
 void attn_fwd_accum(const at::Tensor& q, const at::Tensor& k,
                     const at::Tensor& v, double softmax_scale, bool causal,
                     at::Tensor& acc, at::Tensor& m, at::Tensor& l,
-                    bool carry_in) {
-  fwd_accum_call(nullptr, q, k, v, softmax_scale, causal, acc, m, l, carry_in);
+                    bool carry_in, const c10::optional<at::Tensor>& q_seg,
+                    const c10::optional<at::Tensor>& kv_seg) {
+  fwd_accum_call(nullptr, q, k, v, softmax_scale, causal, acc, m, l, carry_in,
+                 q_seg, kv_seg);
 }
 
 std::vector<at::Tensor> attn_fwd_finalize(const at::Tensor& acc,
@@ -224,11 +299,14 @@ void attn_bwd_accum(const at::Tensor& dout, const at::Tensor& q,
                     const at::Tensor& k, const at::Tensor& v,
                     const at::Tensor& delta, const at::Tensor& lse,
                     double softmax_scale, bool causal, bool deterministic,
-                    at::Tensor& dq, at::Tensor& dk, at::Tensor& dv) {
+                    at::Tensor& dq, at::Tensor& dk, at::Tensor& dv,
+                    const c10::optional<at::Tensor>& q_seg,
+                    const c10::optional<at::Tensor>& kv_seg) {
   check_qkv(dout, "dout");
   check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
+  const SegIds seg = seg_ids(q_seg, kv_seg, q, k);
   TORCH_CHECK(dout.size(0) == B && dout.size(1) == Sq && dout.size(2) == N &&
                   dout.size(3) == D,
               "dout/q shape mismatch");
@@ -246,20 +324,23 @@ void attn_bwd_accum(const at::Tensor& dout, const at::Tensor& q,
   int64_t ds[2] = {delta.stride(0), delta.stride(1)};
   int64_t ls[2] = {lse.stride(0), lse.stride(1)};
   auto stream = at::hip::getCurrentHIPStream().stream();
-  BA_CALL(bahip_attn_bwd_gqa(
+  BA_CALL(bahip_attn_bwd_seg(
       dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
       delta.data_ptr<float>(), lse.data_ptr<float>(), dq.data_ptr<float>(),
       dk.data_ptr<float>(), dv.data_ptr<float>(), B, Sq, Sk, N, k.size(2), D,
       Strides3(dout), Strides3(q), Strides3(k), Strides3(v), ds, ls,
       Strides3(dq), Strides3(dk), Strides3(dv), (float)softmax_scale,
-      causal ? 1 : 0, deterministic ? 1 : 0, dtype_code(q), stream));
+      causal ? 1 : 0, deterministic ? 1 : 0, dtype_code(q), seg.q, seg.kv,
+      seg.q_sb, seg.kv_sb, seg.ws_ptr(), seg.ws_bytes(), stream));
 }
 
 std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
                                  const at::Tensor& k, const at::Tensor& v,
                                  const at::Tensor& delta,
                                  const at::Tensor& lse, double softmax_scale,
-                                 bool causal, bool deterministic) {
+                                 bool causal, bool deterministic,
+                                 const c10::optional<at::Tensor>& q_seg,
+                                 const c10::optional<at::Tensor>& kv_seg) {
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
   // zero-filled: the kernels accumulate, so this equals fresh outputs
@@ -269,7 +350,7 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
   auto dk = at::zeros({B, Sk, Nk, D}, q.options().dtype(at::kFloat));
   auto dv = at::zeros({B, Sk, Nk, D}, q.options().dtype(at::kFloat));
   attn_bwd_accum(dout, q, k, v, delta, lse, softmax_scale, causal,
-                 deterministic, dq, dk, dv);
+                 deterministic, dq, dk, dv, q_seg, kv_seg);
   return {dq, dk, dv};
 }
 
@@ -332,9 +413,21 @@ at::Tensor tr16_probe(int64_t mode) {
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-  m.def("attn_fwd", &attn_fwd, "BurstAttention fwd tile (gfx950)");
+  m.def("attn_fwd", &attn_fwd, "BurstAttention fwd tile (gfx950)",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("softmax_scale"),
+        py::arg("causal"), py::arg("q_seg") = py::none(),
+        py::arg("kv_seg") = py::none());
   m.def("attn_fwd_accum", &attn_fwd_accum,
-        "carry-in accumulator fwd tile (in-kernel LSE merge)");
+        "carry-in accumulator fwd tile (in-kernel LSE merge)", py::arg("q"),
+        py::arg("k"), py::arg("v"), py::arg("softmax_scale"),
+        py::arg("causal"), py::arg("acc"), py::arg("m"), py::arg("l"),
+        py::arg("carry_in"), py::arg("q_seg") = py::none(),
+        py::arg("kv_seg") = py::none());
+  m.def("attn_seg_prepass", &attn_seg_prepass,
+        "segment-id pre-pass alone: the int32 workspace (tile summaries and "
+        "block ranges of both side pairs)");
+  m.def("attn_seg_workspace_bytes", &bahip_attn_seg_workspace_bytes,
+        "bytes of the segment-id pre-pass workspace of a (B, Sq, Sk) call");
   m.def("attn_fwd_finalize", &attn_fwd_finalize,
         "o = acc/l (cast), lse from state");
   m.def("attn_vt_image", &attn_vt_image,
@@ -345,9 +438,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "the current knobs; 0 = in-kernel transpose");
   m.def("attn_bwd_preprocess", &attn_bwd_preprocess, "delta = rowsum(o*do)",
         py::arg("o"), py::arg("dout"), py::arg("out") = py::none());
-  m.def("attn_bwd", &attn_bwd, "BurstAttention bwd tile (gfx950)");
+  m.def("attn_bwd", &attn_bwd, "BurstAttention bwd tile (gfx950)",
+        py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("delta"), py::arg("lse"), py::arg("softmax_scale"),
+        py::arg("causal"), py::arg("deterministic"),
+        py::arg("q_seg") = py::none(), py::arg("kv_seg") = py::none());
   m.def("attn_bwd_accum", &attn_bwd_accum,
-        "bwd tile accumulating into fp32 dq/dk/dv views");
+        "bwd tile accumulating into fp32 dq/dk/dv views", py::arg("dout"),
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("delta"),
+        py::arg("lse"), py::arg("softmax_scale"), py::arg("causal"),
+        py::arg("deterministic"), py::arg("dq"), py::arg("dk"), py::arg("dv"),
+        py::arg("q_seg") = py::none(), py::arg("kv_seg") = py::none());
   m.def("mfma_probe", &mfma_probe, "32x32x16 MFMA layout probe");
   m.def("tr16_probe", &tr16_probe, "ds_read_tr16_b64 semantics probe");
   m.def("attn_fwd_asm_load", &attn_fwd_asm_load,

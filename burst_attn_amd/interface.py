@@ -28,6 +28,16 @@ convention).  K/V travel the ring UNEXPANDED (the forward payload and the
 comm buffers shrink N/Nk-fold), and ``k.grad``/``v.grad`` have Nk heads:
 the kernels sum each group's query heads in place.
 
+Packed sequences: the trailing keyword ``segment_ids`` (this rank's
+``[B, S_local]`` int32/int64 ids, in the layout of its q/k/v rows; see
+``segments.py``) restricts every token to keys of its own id, on top of
+``causal``.  The kv ids travel with {k, v} in the forward, the q ids with
+{delta-or-o, grad_output, q, lse} in the backward, and each round hands the
+tile provider ``seg=(q_ids[:, q_rows], kv_ids[:, kv_rows])``.  The ids are
+compared for equality only, so they need nothing from ``tile_window`` and
+the causal flag of a tile keeps its meaning.  Without ``segment_ids``
+neither the payloads nor the provider calls change.
+
 The two causal load-balancing layouts (see oracle/partition.py) run the
 same code: ``OpBurstAttn`` (zigzag: rank r holds global chunks [r] and
 [2W-1-r]) and ``OpBurstAttnStrip`` (striped: token t on rank t mod W) only
@@ -162,6 +172,32 @@ def _check_heads(q, k, v):
         )
 
 
+def _check_segment_ids(segment_ids, q):
+    """None, or this rank's ids as contiguous int32 ``[B, S_local]`` on q's
+    device (converted once, here)."""
+    if segment_ids is None:
+        return None
+    if not isinstance(segment_ids, torch.Tensor):
+        raise ValueError(
+            f"segment_ids must be a tensor, got {type(segment_ids).__name__}"
+        )
+    if segment_ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError(
+            f"segment_ids must be int32 or int64, got {segment_ids.dtype}"
+        )
+    if tuple(segment_ids.shape) != (q.shape[0], q.shape[1]):
+        raise ValueError(
+            "segment_ids must be [B, S_local] = "
+            f"{(q.shape[0], q.shape[1])} like q's rows, got "
+            f"{tuple(segment_ids.shape)}"
+        )
+    if segment_ids.device != q.device:
+        raise ValueError(
+            f"segment_ids is on {segment_ids.device}, q on {q.device}"
+        )
+    return segment_ids.to(torch.int32).contiguous()
+
+
 def burst_attn_func(
     q: torch.Tensor,
     k: torch.Tensor,
@@ -173,11 +209,14 @@ def burst_attn_func(
     deterministic: bool = False,
     process_group=None,
     double_group=[None, None],
+    *,
+    segment_ids: torch.Tensor = None,
 ):
     _check_heads(q, k, v)
     return OpBurstAttn.apply(
         q, k, v, softmax_scale, flash, causal, optimize_bwd_comm,
         deterministic, process_group, double_group,
+        _check_segment_ids(segment_ids, q),
     )
 
 
@@ -192,19 +231,25 @@ def burst_attn_func_striped(
     deterministic: bool = False,
     process_group=None,
     double_group=[None, None],
+    *,
+    segment_ids: torch.Tensor = None,
 ):
     _check_heads(q, k, v)
     return OpBurstAttnStrip.apply(
         q, k, v, softmax_scale, flash, causal, optimize_bwd_comm,
         deterministic, process_group, double_group,
+        _check_segment_ids(segment_ids, q),
     )
 
 
 def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
                   causal=False, optimize_bwd_comm=False, deterministic=False,
-                  process_group=None, double_group=[None, None]):
-    """Forward of both layouts: q stays, {k, v} travel the ring."""
+                  process_group=None, double_group=[None, None],
+                  segment_ids=None):
+    """Forward of both layouts: q stays, {k, v} travel the ring (with the
+    kv ids, when there are segment ids)."""
     _check_flash_arg(flash)
+    ctx.segment_ids = ids = segment_ids
     ctx.dq_group = double_group
     if isinstance(double_group[0], tuple):
         # [(group, dq_group), (group2, dq_group2)] — separate backward dq
@@ -225,20 +270,28 @@ def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
     W, rank = ring.world_size, ring.rank
     ori_k, ori_v = replicate(k), replicate(v)
     comm_bufs = [torch.empty_like(k), torch.empty_like(v)]
+    kv_ids = None
+    if ids is not None:
+        kv_ids = replicate(ids)
+        comm_bufs.append(torch.empty_like(ids))
     state = None  # provider-owned carry-in accumulator (in-kernel merge)
     record = []
     for r in range(1, W + 1):
         src = get_partition_id(double_group, r, process_group)
         record.append(src)
         qw, kw, tile_causal = tile_window(layout, rank, src, causal, q.shape[1])
+        payload = [k, v] if ids is None else [k, v, kv_ids]
         if r != W:
-            ring.double_ring_send_recv([k, v], comm_bufs, r)
+            ring.double_ring_send_recv(payload, comm_bufs, r)
             ring.commit()
+        seg = {} if ids is None else {"seg": (ids[:, qw], kv_ids[:, kw])}
         state = P.fwd_accum(state, q[:, qw], k[:, kw], v[:, kw], scale,
-                            tile_causal, row_offset=qw.start or 0)
+                            tile_causal, row_offset=qw.start or 0, **seg)
         if r != W:
-            kv, comm_bufs = _record_stream(*comm_bufs), [k, v]
-            k, v = kv
+            recv, comm_bufs = _record_stream(*comm_bufs), payload
+            k, v = recv[:2]
+            if ids is not None:
+                kv_ids = recv[2]
             ring.wait()
     _logger.info("fwd record of rank %d: %s", get_rank(), record)
     # o in q.dtype, lse [B,N,S] fp32 (reference :250-252 semantics)
@@ -286,6 +339,10 @@ def _ring_backward(layout, ctx, grad_output):
     """Backward of both layouts: k, v, dk, dv stay; {delta-or-o,
     grad_output, q, lse} travel one ring and their dq a second one."""
     q, k, v, lse, o = ctx.saved_tensors
+    # this rank's ids: the kv side for the whole backward; a copy of them
+    # travels with q as the q side
+    ids = ctx.segment_ids
+    q_ids = None if ids is None else replicate(ids)
     P = get_tile_provider()
     scale, causal = ctx.softmax_scale, ctx.causal
     grad_output = grad_output.contiguous()
@@ -314,11 +371,16 @@ def _ring_backward(layout, ctx, grad_output):
         )
     dq_hop = _TravellingDq(dq_ring, q, dq)
     read_bufs = [torch.empty_like(t) for t in (dlt, grad_output, q, lse)]
+    if ids is not None:
+        read_bufs.append(torch.empty_like(q_ids))
     for r in range(1, W + 1):
         src = get_partition_id(double_group, r, group)
         qw, kw, tile_causal = tile_window(layout, src, rank, causal, q.shape[1])
+        payload = [dlt, grad_output, q, lse]
+        if ids is not None:
+            payload.append(q_ids)
         if r != W:
-            ring.double_ring_send_recv([dlt, grad_output, q, lse], read_bufs, r)
+            ring.double_ring_send_recv(payload, read_bufs, r)
             ring.commit()
         if r != 1:
             dq_hop.start(dq, r)
@@ -331,13 +393,13 @@ def _ring_backward(layout, ctx, grad_output):
             grad_output[:, qw], q[:, qw], k[:, kw], v[:, kw],
             delta[:, :, qw], lse[:, :, qw], scale, tile_causal,
             ctx.deterministic, tgt[:, qw], dk[:, kw], dv[:, kw],
+            **({} if ids is None else {"seg": (q_ids[:, qw], ids[:, kw])}),
         )
         if r != W:
-            recv, read_bufs = (
-                _record_stream(*read_bufs),
-                [dlt, grad_output, q, lse],
-            )
-            dlt, grad_output, q, lse = recv
+            recv, read_bufs = _record_stream(*read_bufs), payload
+            dlt, grad_output, q, lse = recv[:4]
+            if ids is not None:
+                q_ids = recv[4]
         ring.wait()
         if r != 1:
             dq = dq_hop.finish(dq)
@@ -349,7 +411,7 @@ def _ring_backward(layout, ctx, grad_output):
     dq = dq_hop.finish(dq)
     return (
         dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype),
-        None, None, None, None, None, None, None,
+        None, None, None, None, None, None, None, None,
     )
 
 

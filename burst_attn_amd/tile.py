@@ -38,11 +38,24 @@ dk/dv are the sum over the G query heads of each group; lse and delta
 stay per query head ([B, N, S]).  Nk == N is plain multi-head attention.
 No signature carries G: the shapes do.
 
+Segment ids (packed sequences): ``fwd``, ``fwd_accum``, ``bwd`` and
+``bwd_accum`` take an optional keyword ``seg=(q_seg, kv_seg)``, two int32
+tensors ``[B, Sq]`` and ``[B, Sk]`` with a contiguous last dim, on q's
+device.  Pair (q row i, kv row j) is then visible iff
+``q_seg[b, i] == kv_seg[b, j]``, on top of ``causal``; no id value is
+special.  The ids belong to the rows actually passed: ``fwd_accum`` slices
+nothing itself, its caller hands in the windowed views that match its
+windowed q and k/v.  A row that sees no key gives ``o = 0``, ``lse = -inf``
+and zero gradients.  A caller without ids passes no ``seg`` keyword at all,
+so a provider that predates it keeps working for id-free calls.
+
 The default provider is the gfx950 HIP extension and FAILS LOUDLY if the
 extension is missing on a GPU machine — there is no CPU/eager fallback in
 the product path.  Tests may inject an oracle-backed provider via
 ``_set_tile_provider_for_testing`` (test infrastructure only).
 """
+
+import functools
 
 import torch
 
@@ -84,22 +97,28 @@ class HipTileProvider:
                                         syms["bf16_accum"])
             self._asm_fwd = True
 
-    def fwd(self, q, k, v, scale, causal):
-        return self._ext.attn_fwd(q, k, v, float(scale), bool(causal))
+    def fwd(self, q, k, v, scale, causal, seg=None):
+        q_seg, kv_seg = seg if seg is not None else (None, None)
+        return self._ext.attn_fwd(q, k, v, float(scale), bool(causal),
+                                  q_seg, kv_seg)
 
     def bwd_preprocess(self, o, do, out=None):
         return self._ext.attn_bwd_preprocess(o, do, out)
 
-    def bwd(self, do, q, k, v, delta, lse, scale, causal, deterministic):
+    def bwd(self, do, q, k, v, delta, lse, scale, causal, deterministic,
+            seg=None):
+        q_seg, kv_seg = seg if seg is not None else (None, None)
         return self._ext.attn_bwd(
-            do, q, k, v, delta, lse, float(scale), bool(causal), bool(deterministic)
+            do, q, k, v, delta, lse, float(scale), bool(causal),
+            bool(deterministic), q_seg, kv_seg,
         )
 
     def bwd_accum(self, do, q, k, v, delta, lse, scale, causal, deterministic,
-                  dq, dk, dv):
+                  dq, dk, dv, seg=None):
+        q_seg, kv_seg = seg if seg is not None else (None, None)
         self._ext.attn_bwd_accum(
             do, q, k, v, delta, lse, float(scale), bool(causal),
-            bool(deterministic), dq, dk, dv,
+            bool(deterministic), dq, dk, dv, q_seg, kv_seg,
         )
 
     def merge(self, o, lse, o_i, lse_i):
@@ -109,11 +128,16 @@ class HipTileProvider:
     # state = (acc fp32 [B,S,N,D] unnormalised O, m fp32 [B,N,S] exp2-domain
     # running max, l fp32 [B,N,S] running sum) over the rank's FULL chunk;
     # row_offset targets the zigzag-half / striped-shift row windows.
-    def fwd_accum(self, state, q, k, v, scale, causal, row_offset=0):
-        # the .s-built module carries the D=128 production variants only
-        accum = (self._ext.attn_fwd_accum_asm
-                 if self._asm_fwd and q.shape[3] == 128
-                 else self._ext.attn_fwd_accum)
+    def fwd_accum(self, state, q, k, v, scale, causal, row_offset=0, seg=None):
+        # the .s-built module carries the D=128 production variants only,
+        # and no segment form: with ids the in-binary kernel runs
+        if self._asm_fwd and q.shape[3] == 128 and seg is None:
+            accum = self._ext.attn_fwd_accum_asm
+        elif seg is not None:
+            accum = functools.partial(self._ext.attn_fwd_accum,
+                                      q_seg=seg[0], kv_seg=seg[1])
+        else:
+            accum = self._ext.attn_fwd_accum
         if state is None:
             assert row_offset == 0, "state is created by a full-row round"
             B, S, N, D = q.shape

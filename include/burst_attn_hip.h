@@ -43,6 +43,34 @@
  *     BAHIP_ERR_UNSUPPORTED.  The BA_BWD_FUSED=1/2 and BA_BWD_DK_FLIP=1
  *     experiment plans are equal-heads only and return
  *     BAHIP_ERR_UNSUPPORTED when Nk != N.
+ *   - segment ids (packed sequences): the *_seg entry points take
+ *     q_seg int32 [B, Sq] and kv_seg int32 [B, Sk] (seq stride 1, a batch
+ *     stride each in elements; a window of a longer row is a base pointer).
+ *     Pair (q row i, kv row j) is visible iff q_seg[i] == kv_seg[j] and, with
+ *     causal, the causal rule holds as well.  No id value is special: ids
+ *     may be negative, sparse and unsorted.  Both pointers null is exactly
+ *     the entry point without ids; one of the two null returns
+ *     BAHIP_ERR_SEGMENT_IDS.  A pre-pass on `stream` writes, into
+ *     seg_workspace (bahip_attn_seg_workspace_bytes(B, Sq, Sk) bytes, one
+ *     size for forward and backward, reusable once the call is enqueued),
+ *     the (min, max) id of every 64-row tile and per 256-row block the range
+ *     of tiles whose (min, max) overlaps the block's; workgroups visit only
+ *     that range and a wave skips a tile whose (min, max) misses its rows'.
+ *     With non-decreasing ids on both sides a tile that shares no id with a
+ *     block is neither loaded nor computed; for arbitrary ids the test is
+ *     conservative and the results are still exact.  A q row that sees no
+ *     key (possible in direct rectangular calls only; in the ring every row
+ *     sees itself): the stateless forward gives o = 0, lse = -inf; a
+ *     carry_in = 0 accumulate call leaves acc = 0, l = 0 and an m that later
+ *     rounds merge correctly; a carry_in = 1 call leaves the row's state
+ *     untouched; bahip_attn_fwd_finalize gives o = 0, lse = -inf for an
+ *     l == 0 row; the backward adds exactly zero from and to such rows.
+ *     Ids are supported by the default forward variant and the default
+ *     backward plan only: with ids, a BA_FWD_* selection of another variant,
+ *     BA_BWD_FUSED=1/2, BA_BWD_DK_FLIP=1 or BA_DQ_PIPE=1 returns
+ *     BAHIP_ERR_UNSUPPORTED naming the knob, and nothing is launched.  The
+ *     forward with ids transposes V in the kernel whatever BA_FWD_VT says
+ *     (its V^T workspace argument is ignored) and never uses hip_function.
  *   - stream is a hipStream_t.
  * Returns 0 on success; nonzero = error.  Every nonzero return sets the
  * calling thread's bahip_last_error() message and every success clears it.
@@ -68,6 +96,8 @@ extern "C" {
                                          BA_DKQ_DBG outside its set */
 #define BAHIP_ERR_WORKSPACE 1005      /* V^T image workspace null or too
                                          small; nothing is launched */
+
+#define BAHIP_ERR_SEGMENT_IDS 1006    /* one of q_seg / kv_seg is null */
 
 const char* bahip_last_error(void);
 
@@ -220,6 +250,61 @@ int bahip_attn_bwd_gqa(
     const int64_t dv_strides[3],
     float softmax_scale, int causal, int deterministic, int dtype,
     void* stream);
+
+/* ---- segment ids (see "segment ids" above) -----------------------------
+ * bahip_attn_fwd_gqa_ws, bahip_attn_fwd_accum_gqa_ws and bahip_attn_bwd_gqa
+ * with per-token ids and the pre-pass workspace.  The segment workspace is
+ * also named BAHIP_ERR_WORKSPACE when null or too small. */
+int64_t bahip_attn_seg_workspace_bytes(int64_t B, int64_t Sq, int64_t Sk);
+/* The pre-pass alone, both side pairs (what bahip_attn_bwd_seg runs; the
+ * forwards run the q-owning pair only).  The workspace then holds, as
+ * 32-bit words in this order: flags [2][B] (kv, q: the side's ids decrease
+ * somewhere), kv tile (min, max) [B][ceil(Sk/64)][2], q block ranges
+ * [B][ceil(Sq/256)][2] over kv tiles, q tile (min, max) [B][ceil(Sq/64)][2],
+ * kv block ranges [B][ceil(Sk/256)][2] over q tiles. */
+int bahip_attn_seg_prepass(
+    const int32_t* q_seg, const int32_t* kv_seg,
+    int64_t q_seg_stride, int64_t kv_seg_stride,
+    int64_t B, int64_t Sq, int64_t Sk,
+    void* seg_workspace, int64_t seg_workspace_bytes, void* stream);
+int bahip_attn_fwd_seg(
+    const void* q, const void* k, const void* v,
+    float* o, float* lse,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3],
+    const int64_t k_strides[3],
+    const int64_t v_strides[3],
+    float softmax_scale, int causal, int dtype,
+    void* workspace, int64_t workspace_bytes,
+    const int32_t* q_seg, const int32_t* kv_seg,
+    int64_t q_seg_stride, int64_t kv_seg_stride,
+    void* seg_workspace, int64_t seg_workspace_bytes, void* stream);
+int bahip_attn_fwd_accum_seg(
+    void* hip_function,
+    const void* q, const void* k, const void* v,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    float* acc, float* m, float* l, const int64_t acc_strides[3],
+    const int64_t ml_strides[2], int carry_in,
+    void* workspace, int64_t workspace_bytes,
+    const int32_t* q_seg, const int32_t* kv_seg,
+    int64_t q_seg_stride, int64_t kv_seg_stride,
+    void* seg_workspace, int64_t seg_workspace_bytes, void* stream);
+int bahip_attn_bwd_seg(
+    const void* dout, const void* q, const void* k, const void* v,
+    const float* delta, const float* lse,
+    float* dq, float* dk, float* dv,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t do_strides[3], const int64_t q_strides[3],
+    const int64_t k_strides[3], const int64_t v_strides[3],
+    const int64_t delta_strides[2], const int64_t lse_strides[2],
+    const int64_t dq_strides[3], const int64_t dk_strides[3],
+    const int64_t dv_strides[3],
+    float softmax_scale, int causal, int deterministic, int dtype,
+    const int32_t* q_seg, const int32_t* kv_seg,
+    int64_t q_seg_stride, int64_t kv_seg_stride,
+    void* seg_workspace, int64_t seg_workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
