@@ -24,6 +24,15 @@ b = seq / doc-len batch of single documents (the same visible work), and
 the segment pre-pass alone at 65536 and 1048576 tokens.  TFLOPS of the
 packed rows count the visible pairs only.
 
+Sliding windows:
+  python benchmarks/sweep.py --window 4096 --window 16384
+runs, at --seq (65536), dense causal and then causal with each --window
+L[,R] (window_size=(L, R); R defaults to 0), and reports next to each time
+its ratio to the dense causal row and the ideal ratio: the (256-row block,
+64-row tile) pairs that hold a visible pair under the window, over those
+under the causal triangle, counted with the arithmetic of
+csrc/band_support.h.  TFLOPS of the window rows count the visible pairs only.
+
 Row fields mirror the reference's results_torch.jsonl semantics.
 """
 
@@ -145,6 +154,64 @@ def bench_packed(args, s, n, nk, d, doc_lens, steps, warmup):
         "fwd_ms": round(t_f * 1e3, 2),
         "fwd_tflops_per_gpu": round(f / t_f / 1e12, 2),
         "fwdbwd_ms": round(t_fb * 1e3, 2),
+        "fwdbwd_tflops_per_gpu": round(3.5 * f / t_fb / 1e12, 2),
+    }
+
+
+def band_tile_pairs(lo, hi, s_own, s_str):
+    """csrc/band_support.h's ba_band_tile_pairs, restated: the (256-row own
+    block, 64-row streamed tile) pairs that hold a pair with
+    lo <= own - streamed <= hi (tests/test_band_support_cpu.py pins this to
+    the header)."""
+    n = 0
+    for r0 in range(0, s_own, 256):
+        r1 = min(r0 + 255, s_own - 1)
+        s0, s1 = max(r0 - hi, 0), min(r1 - lo, s_str - 1)
+        if lo <= hi and s0 <= s1:
+            n += s1 // 64 - s0 // 64 + 1
+    return n
+
+
+def bench_window(args, s, n, nk, d, window, dense, steps, warmup):
+    """Causal forward and forward+backward under window_size=window, next to
+    the dense causal row `dense` of the same run."""
+    from burst_attn_amd import burst_attn_func
+
+    dtype = torch.float16 if args.dtype == "fp16" else torch.bfloat16
+    g = torch.Generator().manual_seed(1000)
+    mk = lambda h=n: torch.randn(1, s, h, d, generator=g).to(dtype).cuda()
+    q, k, v, do = mk(), mk(nk), mk(nk), mk()
+
+    def fwd():
+        with torch.no_grad():
+            burst_attn_func(q, k, v, None, "cuda", True, window_size=window)
+
+    def fwdbwd():
+        qg, kg, vg = (t.detach().requires_grad_() for t in (q, k, v))
+        o = burst_attn_func(qg, kg, vg, None, "cuda", True,
+                            window_size=window)
+        torch.autograd.grad(o, (qg, kg, vg), do)
+
+    t_f = timeit(fwd, steps, warmup)
+    t_fb = timeit(fwdbwd, steps, warmup)
+    left = window[0]
+    hi = s if left < 0 else left
+    i = torch.arange(s, dtype=torch.float64)
+    pairs = float((torch.minimum(i, torch.full_like(i, hi)) + 1).sum())
+    f = 4.0 * pairs * n * d
+    big = 1 << 30
+    ideal = band_tile_pairs(0, hi, s, s) / band_tile_pairs(0, big, s, s)
+    return {
+        "method": "burst_window", "b": 1, "s": s, "n": n, "nk": nk, "d": d,
+        "causal": True, "window": list(window), "wsize": 1,
+        "visible_frac": round(pairs / (s * (s + 1) / 2), 4),
+        "ideal_tile_ratio": round(ideal, 4),
+        "dtype": args.dtype,
+        "fwd_ms": round(t_f * 1e3, 2),
+        "fwd_ratio_to_causal": round(t_f * 1e3 / dense["fwd_ms"], 4),
+        "fwd_tflops_per_gpu": round(f / t_f / 1e12, 2),
+        "fwdbwd_ms": round(t_fb * 1e3, 2),
+        "fwdbwd_ratio_to_causal": round(t_fb * 1e3 / dense["fwdbwd_ms"], 4),
         "fwdbwd_tflops_per_gpu": round(3.5 * f / t_fb / 1e12, 2),
     }
 
@@ -289,6 +356,11 @@ def main():
     p.add_argument("--doc-len", action="append", default=None,
                    help="packed config: document length(s); repeat or give "
                         "a comma list for mixed lengths (default 8192)")
+    p.add_argument("--window", action="append", default=None,
+                   metavar="L[,R]",
+                   help="run dense causal at --seq and causal with "
+                        "window_size=(L, R) (R defaults to 0); repeatable; "
+                        "replaces --configs")
     args = p.parse_args()
     nk = args.heads if args.kv_heads is None else args.kv_heads
     if nk < 1 or args.heads % nk:
@@ -306,7 +378,22 @@ def main():
 
     rows = []
     n, d = args.heads, 128
-    if args.configs == "quick":  # 1-GPU-friendly sweep
+    if args.window:
+        if world != 1:
+            p.error("--window is a one-GPU measurement")
+        windows = []
+        for item in args.window:
+            lr = [int(x) for x in item.split(",")]
+            if len(lr) not in (1, 2) or min(lr) < -1:
+                p.error("--window takes L or L,R with values >= -1")
+            windows.append((lr[0], lr[1] if len(lr) == 2 else 0))
+        dense = bench_burst(args, 1, args.seq, n, d, True, False, False,
+                            args.steps, args.warmup, nk)
+        rows.append(dense)
+        for w in windows:
+            rows.append(bench_window(args, args.seq, n, nk, d, w, dense,
+                                     args.steps, args.warmup))
+    elif args.configs == "quick":  # 1-GPU-friendly sweep
         for s in (16384, 32768, 65536):
             for causal in (False, True):
                 rows.append(bench_burst(args, 1, s, n, d, causal, False, causal,

@@ -89,9 +89,13 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
     float scale, int causal, SEG... seg) {
   using MT = mfma_traits<T>;
   using frag = typename MT::frag;
-  constexpr bool HAS_SEG = sizeof...(SEG) != 0;
-  static_assert(!HAS_SEG || (sizeof...(SEG) == 1 && DQP == 0),
-                "segment ids: the default dq kernel");
+  constexpr bool HAS_BAND = ba_pack_is<ba_band_args, SEG...>;
+  constexpr bool HAS_SEG = sizeof...(SEG) != 0 && !HAS_BAND;
+  constexpr bool HAS_MASK = HAS_SEG || HAS_BAND;
+  static_assert(!HAS_MASK || (sizeof...(SEG) == 1 && DQP == 0),
+                "segment ids / band: the default dq kernel");
+  // band form: the band is the whole mask (the launcher folded causal in)
+  if constexpr (HAS_BAND) causal = 0;
   constexpr int SWZ = (D == 128) ? 15 : 7;   // row-major images (2*D B rows)
   constexpr int SWZ_T = 7;                   // transposed images (128 B rows)
   constexpr int NT = 512;
@@ -178,8 +182,18 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
     kseg = sg.kv_seg + b * sg.kv_sb;
     tmm = sg.tile_mm + (int64_t)b * ((Sk + KVBLK - 1) / KVBLK);
   }
-  const int t_first = HAS_SEG ? trange.x : 0;
-  const int nt = HAS_SEG ? trange.y : nt_shape;
+  // band form: the block's kv tile range is arithmetic (band_support.h)
+  ba_band_args bd = {0, 0};
+  if constexpr (HAS_BAND) {
+    static_assert(KVBLK == BA_BAND_TILE, "band: tiles of band_support.h");
+    bd = ba_band_of(seg...);
+    const ba_tile_range r = ba_band_block_tiles(blockIdx.x, bd, Sq, Sk);
+    trange.x = r.lo;
+    trange.y = r.hi;
+    if (trange.x >= trange.y) return;  // workgroup-uniform, no barrier yet
+  }
+  const int t_first = HAS_MASK ? trange.x : 0;
+  const int nt = HAS_MASK ? trange.y : nt_shape;
 
   auto issue_loads = [&](int tile, u32x4_t* kreg, u32x4_t* vreg) {
     const int kv0 = tile * KVBLK;
@@ -230,6 +244,8 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
       seg_mask = !(mm.x == mm.y && wq_min == wq_max && mm.x == wq_min);
       active = (!causal || (kv0 <= qb + 31)) && mm.y >= wq_min &&
                mm.x <= wq_max;
+    } else if constexpr (HAS_BAND) {
+      active = ba_band_wave_active(qb, kv0, bd);
     } else {
       active = !causal || (kv0 <= qb + 31);
     }
@@ -280,6 +296,8 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
               kv_g < Sk && (!causal || kv_g <= q_row) && q_row < Sq;
           if constexpr (HAS_SEG)
             valid = valid && (!seg_mask || kseg[min(kv_g, Sk - 1)] == qid);
+          if constexpr (HAS_BAND)
+            valid = valid && ba_band_visible(q_row, kv_g, bd);
           const float e = valid ? __builtin_fmaf(st[r], c2, -lse2) : BA_NEG_BIG;
           const float p = ba_exp2(e);
           st[r] = p * (dpt[r] - dlt) * scale;
@@ -356,9 +374,14 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
     float scale, int causal, SEG... seg) {
   using MT = mfma_traits<T>;
   using frag = typename MT::frag;
-  constexpr bool HAS_SEG = sizeof...(SEG) != 0;
-  static_assert(!HAS_SEG || (sizeof...(SEG) == 1 && QBLK == BA_SEG_TILE),
-                "segment ids: q tiles of the pre-pass's tile size");
+  constexpr bool HAS_BAND = ba_pack_is<ba_band_args, SEG...>;
+  constexpr bool HAS_SEG = sizeof...(SEG) != 0 && !HAS_BAND;
+  constexpr bool HAS_MASK = HAS_SEG || HAS_BAND;
+  static_assert(!HAS_MASK || (sizeof...(SEG) == 1 && QBLK == BA_SEG_TILE &&
+                              QBLK == BA_BAND_TILE),
+                "segment ids / band: q tiles of the pre-pass's tile size");
+  // band form: the band is the whole mask (the launcher folded causal in)
+  if constexpr (HAS_BAND) causal = 0;
   constexpr int SWZ = (D == 128) ? 15 : 7;
   constexpr int SWZ_T = 7;
   constexpr int NT = 512;
@@ -447,8 +470,18 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
     qseg = sg.q_seg + b * sg.q_sb;
     tmm = sg.tile_mm + (int64_t)b * ((Sq + QBLK - 1) / QBLK);
   }
-  const int t0 = HAS_SEG ? trange.x : t0_shape;
-  const int nt = HAS_SEG ? trange.y : nt_shape;
+  // band form: the block's q tile range is arithmetic; this kernel owns kv
+  // rows, so it sees the band of (kv row - q row)
+  ba_band_args bd = {0, 0};
+  if constexpr (HAS_BAND) {
+    bd = ba_band_flip(ba_band_of(seg...));
+    const ba_tile_range r = ba_band_block_tiles(blockIdx.x, bd, Sk, Sq);
+    trange.x = r.lo;
+    trange.y = r.hi;
+    if (trange.x >= trange.y) return;  // workgroup-uniform, no barrier yet
+  }
+  const int t0 = HAS_MASK ? trange.x : t0_shape;
+  const int nt = HAS_MASK ? trange.y : nt_shape;
 
   // per-lane lse*log2e and delta for both subtiles of a tile (l2[qs] =
   // {lse2, delta}), loaded straight from global — clamped, branchless
@@ -530,6 +563,8 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
       seg_mask = !(mm.x == mm.y && wk_min == wk_max && mm.x == wk_min);
       active = (!causal || (q0 + QBLK - 1 >= kvb)) && mm.y >= wk_min &&
                mm.x <= wk_max;
+    } else if constexpr (HAS_BAND) {
+      active = ba_band_wave_active(kvb, q0, bd);
     } else {
       active = !causal || (q0 + QBLK - 1 >= kvb);
     }
@@ -587,6 +622,8 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
               q_g < Sq && kv_col < Sk && (!causal || q_g >= kv_col);
           if constexpr (HAS_SEG)
             valid = valid && (!seg_mask || qseg[min(q_g, Sq - 1)] == kid);
+          if constexpr (HAS_BAND)
+            valid = valid && ba_band_visible(kv_col, q_g, bd);
           const float e = valid ? st[r] * c2 : BA_NEG_BIG;
           const float p = ba_exp2(e);
           // MODE_DV: P; MODE_DK: dS
@@ -1146,6 +1183,26 @@ static void launch_dkv_seg(const bwd_dkv_args& a, const ba_seg_args& sg,
                   stream, sg);
 }
 
+// the band forms of the same three kernels: no pre-pass, the band itself
+template <typename T, int D>
+static void launch_dq_band(const bwd_dq_args& a, const ba_band_args& bd,
+                           int64_t B, hipStream_t stream) {
+  const dim3 grid((unsigned)((a.Sq + 255) / 256), (unsigned)a.N, (unsigned)B);
+  launch_acc<T>(bwd_dq_kernel<T, D, 0, ba_band_args>, grid, a, stream, bd);
+}
+template <typename T, int D, int MODE>
+static void launch_dkv_band(const bwd_dkv_args& a, const ba_band_args& bd,
+                            int64_t B, hipStream_t stream) {
+  const dim3 grid((unsigned)((a.Sk + 255) / 256), (unsigned)(a.N / a.G),
+                  (unsigned)B);
+  if (a.G > 1)
+    launch_acc<T>(bwd_dkv_kernel<T, D, MODE, 64, 1, ba_band_args>, grid, a,
+                  stream, bd);
+  else
+    launch_acc<T>(bwd_dkv_kernel<T, D, MODE, 64, 0, ba_band_args>, grid, a,
+                  stream, bd);
+}
+
 struct bwd_dkq_args {
   const void *dout, *q, *k, *v;
   const float *delta, *lse;
@@ -1182,7 +1239,13 @@ struct bwd_seg_call {
   int64_t ws_bytes;
 };
 
-// Shared body of the backward entry points; seg null = the plain call.
+// what bahip_attn_bwd_band adds to the plain call: the band as given
+struct bwd_band_call {
+  int64_t lo, hi;
+};
+
+// Shared body of the backward entry points; seg and band null = the plain
+// call.
 static int bwd_entry(
     const void* dout, const void* q, const void* k, const void* v,
     const float* delta, const float* lse, float* dq, float* dk, float* dv,
@@ -1191,7 +1254,7 @@ static int bwd_entry(
     const int64_t vs[3], const int64_t ds[2], const int64_t ls[2],
     const int64_t dqs[3], const int64_t dks[3], const int64_t dvs[3],
     float scale, int causal, int deterministic, int dtype, void* stream,
-    const bwd_seg_call* seg) {
+    const bwd_seg_call* seg, const bwd_band_call* band = nullptr) {
   (void)deterministic;  // only atomic6 is not deterministic by construction
   if (causal && Sq != Sk)
     return ba_fail(BAHIP_ERR_CAUSAL_SHAPE,
@@ -1270,6 +1333,38 @@ static int bwd_entry(
       return ba_launch_status();
     });
   }
+  if (band) {
+    // the default plan's kernels in their band form
+    if (band->lo > band->hi)
+      return ba_fail(BAHIP_ERR_BAND, "band: lo=%lld is above hi=%lld",
+                     (long long)band->lo, (long long)band->hi);
+    const ba_seg_verdict sv = ba_seg_bwd_support(kn);
+    if (sv.knob)
+      return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                     "%s=%d does not support a band (default backward plan "
+                     "only)",
+                     sv.knob, sv.value);
+    if (B < 1 || B > 65535 || Sq < 1 || Sk < 1)
+      return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                     "band: unsupported shape B=%d Sq=%d Sk=%d", (int)B,
+                     (int)Sq, (int)Sk);
+    // causal cuts the band at the diagonal: the band kernels never read
+    // `causal`
+    const ba_band_args bd = {
+        ba_band_clamp(causal && band->lo < 0 ? 0 : band->lo),
+        ba_band_clamp(band->hi)};
+    const hipStream_t st = (hipStream_t)stream;
+    return ba_dispatch_td(D, dtype, [&](auto td) {
+      using T = typename decltype(td)::type;
+      constexpr int TD = decltype(td)::D;
+      launch_dq_band<T, TD>(dqa, bd, B, st);
+      BA_CHECK_LAUNCH();
+      launch_dkv_band<T, TD, 0>(dva, bd, B, st);
+      BA_CHECK_LAUNCH();
+      launch_dkv_band<T, TD, 1>(dka, bd, B, st);
+      return ba_launch_status();
+    });
+  }
   const bwd_dkq_args dkqa = {
       dout, q, k, v, delta, lse, dq, dk, dv, iSq, iSk, iN,
       gs[0], gs[1], gs[2], qs[0], qs[1], qs[2], ks[0], ks[1], ks[2],
@@ -1332,6 +1427,21 @@ extern "C" int bahip_attn_bwd_seg(
   return bwd_entry(dout, q, k, v, delta, lse, dq, dk, dv, B, Sq, Sk, N, Nk, D,
                    gs, qs, ks, vs, ds, ls, dqs, dks, dvs, scale, causal,
                    deterministic, dtype, stream, q_seg ? &sc : nullptr);
+}
+
+extern "C" int bahip_attn_bwd_band(
+    const void* dout, const void* q, const void* k, const void* v,
+    const float* delta, const float* lse, float* dq, float* dk, float* dv,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t gs[3], const int64_t qs[3], const int64_t ks[3],
+    const int64_t vs[3], const int64_t ds[2], const int64_t ls[2],
+    const int64_t dqs[3], const int64_t dks[3], const int64_t dvs[3],
+    float scale, int causal, int deterministic, int dtype, int64_t band_lo,
+    int64_t band_hi, void* stream) {
+  const bwd_band_call bc = {band_lo, band_hi};
+  return bwd_entry(dout, q, k, v, delta, lse, dq, dk, dv, B, Sq, Sk, N, Nk, D,
+                   gs, qs, ks, vs, ds, ls, dqs, dks, dvs, scale, causal,
+                   deterministic, dtype, stream, nullptr, &bc);
 }
 
 // the equal-heads symbol: Nk = N

@@ -27,6 +27,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "band_support.h"
+
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
@@ -148,6 +150,26 @@ struct ba_seg_args {
 __device__ __forceinline__ ba_seg_args ba_seg_of() { return {}; }
 __device__ __forceinline__ ba_seg_args ba_seg_of(const ba_seg_args& s) {
   return s;
+}
+
+// ---- band masks (sliding windows) --------------------------------------
+// The band form of a kernel takes one ba_band_args {lo, hi} (band_support.h)
+// in the same trailing pack: pair (q row i, kv row j) is visible iff
+// lo <= i - j <= hi, and nothing else masks but the tensors' own ranges (the
+// band form never reads `causal`; the launcher folds it into lo).  What the
+// pack holds selects the form at compile time.
+template <typename A, typename B>
+struct ba_same_t {
+  static constexpr bool value = false;
+};
+template <typename A>
+struct ba_same_t<A, A> {
+  static constexpr bool value = true;
+};
+template <typename A, typename... P>
+constexpr bool ba_pack_is = sizeof...(P) == 1 && (ba_same_t<A, P>::value && ...);
+__device__ __forceinline__ ba_band_args ba_band_of(const ba_band_args& b) {
+  return b;
 }
 
 // min and max of x over the wave, as wave-uniform (scalar) values

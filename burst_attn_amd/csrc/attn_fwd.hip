@@ -123,10 +123,19 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
     int64_t ml_sb, int64_t ml_sh, int carry_in, SEG... seg) {
   using MT = mfma_traits<T>;
   using frag = typename MT::frag;
-  constexpr bool HAS_SEG = sizeof...(SEG) != 0;
-  static_assert(!HAS_SEG || (sizeof...(SEG) == 1 && VPATH == 0 && SUBT == 1 &&
-                             NT == 512 && NBUF == 2 && KREG == 0 && VSRC == 0),
-                "segment ids: the default variant, V transposed in-kernel");
+  constexpr bool HAS_BAND = ba_pack_is<ba_band_args, SEG...>;
+  constexpr bool HAS_SEG = sizeof...(SEG) != 0 && !HAS_BAND;
+  // either form: entries can be masked inside the tensors' ranges, so a row
+  // may see no key (weight-0 select, l = 0 epilogue)
+  constexpr bool HAS_MASK = HAS_SEG || HAS_BAND;
+  static_assert(!HAS_MASK || (sizeof...(SEG) == 1 && VPATH == 0 && SUBT == 1 &&
+                              NT == 512 && NBUF == 2 && KREG == 0 && VSRC == 0),
+                "segment ids / band: the default variant, V transposed "
+                "in-kernel");
+  static_assert(!HAS_BAND || (KVBLK == BA_BAND_TILE && NT / 2 == BA_BAND_BLOCK),
+                "band: the tile sizes of band_support.h");
+  // band form: the band is the whole mask (the launcher folded causal in)
+  if constexpr (HAS_BAND) causal = 0;
   constexpr int SWZ_K = (D == 128) ? 15 : 7;  // K image rows are 2*D bytes
   constexpr int SWZ_V = 7;                    // V^T image rows are 128 bytes
   constexpr int PT = (KVBLK * D / 8) / NT;
@@ -246,8 +255,38 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
     kseg = sg.kv_seg + b * sg.kv_sb;
     tmm = sg.tile_mm + (int64_t)b * ((Sk + KVBLK - 1) / KVBLK);
   }
-  const int t_first = HAS_SEG ? trange.x : 0;
-  const int nt = HAS_SEG ? trange.y : nt_shape;
+  // band form: the block's tile range is arithmetic (band_support.h)
+  ba_band_args bd = {0, 0};
+  bool band_full = false;  // the current tile holds no masked entry
+  if constexpr (HAS_BAND) {
+    bd = ba_band_of(seg...);
+    const ba_tile_range r = ba_band_block_tiles(blockIdx.x, bd, Sq, Sk);
+    trange.x = r.lo;
+    trange.y = r.hi;
+    if (trange.x >= trange.y) {
+      // workgroup-uniform, no barrier yet; what the segment form writes
+      if (q_row < Sq && !(OUT_STATE && carry_in)) {
+        float* row = OUT_STATE
+                         ? st_acc + b * a_sb + (int64_t)q_row * a_ss + n * a_sh
+                         : o + (((int64_t)b * Sq + q_row) * N + n) * D;
+#pragma unroll
+        for (int dt = 0; dt < D / 32; ++dt)
+#pragma unroll
+          for (int r2 = 0; r2 < 16; ++r2) row[dt * 32 + ba_crow(r2, hi)] = 0.f;
+        if (hi == 0) {
+          if (OUT_STATE) {
+            st_m[b * ml_sb + n * ml_sh + q_row] = BA_NEG_BIG;
+            st_l[b * ml_sb + n * ml_sh + q_row] = 0.f;
+          } else {
+            lse[((int64_t)b * N + n) * Sq + q_row] = -__builtin_inff();
+          }
+        }
+      }
+      return;
+    }
+  }
+  const int t_first = HAS_MASK ? trange.x : 0;
+  const int nt = HAS_MASK ? trange.y : nt_shape;
   static_assert(SUBT != 2 || (NBUF == 4 && VPATH == 0),
                 "the T15 pipeline needs NBUF=4 and the V^T image");
   static_assert(SUBT != 3 || (NBUF == 4 && VPATH == 0 && NT == 256),
@@ -297,6 +336,9 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
       if constexpr (HAS_SEG) {
         if (seg_mask && kseg[min(kv_g, Sk - 1)] != qid) s[r] = BA_NEG_BIG;
       }
+      if constexpr (HAS_BAND) {
+        if (!ba_band_visible(q_row, kv_g, bd)) s[r] = BA_NEG_BIG;
+      }
     }
   };
   // row max in the exp2 domain.  The softmax scale is folded into the exp
@@ -337,18 +379,30 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
   auto softmax_tail = [&](f32x16_t& s, float tm, frag* pf) BA_STEP {
     rescale(tm);
     float rowsum = 0.f;
+    // band form, full tile (wave-uniform): no entry is masked and every
+    // row's max is a real score after the rescale above, so the plain exp
+    // serves and the select below stays out of the steady loop
+    if (HAS_BAND && band_full) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      // segment form: a masked entry weighs exactly 0 even while the row's
-      // running max is still at the masked level (a row whose tiles so far
-      // held no visible key), where the exponent below would not be small
-      if constexpr (HAS_SEG) {
-        const bool masked = s[r] == BA_NEG_BIG;
-        s[r] = masked ? 0.f : ba_exp2(__builtin_fmaf(s[r], c2, -m2));
-      } else {
+      for (int r = 0; r < 16; ++r) {
         s[r] = ba_exp2(__builtin_fmaf(s[r], c2, -m2));
+        rowsum += s[r];
       }
-      rowsum += s[r];
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        // segment form: a masked entry weighs exactly 0 even while the
+        // row's running max is still at the masked level (a row whose tiles
+        // so far held no visible key), where the exponent below would not
+        // be small
+        if constexpr (HAS_MASK) {
+          const bool masked = s[r] == BA_NEG_BIG;
+          s[r] = masked ? 0.f : ba_exp2(__builtin_fmaf(s[r], c2, -m2));
+        } else {
+          s[r] = ba_exp2(__builtin_fmaf(s[r], c2, -m2));
+        }
+        rowsum += s[r];
+      }
     }
     if (HSWAP) {
       float lo, hi2;
@@ -598,6 +652,11 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
                mm.x <= wq_max;
       full = (kv0 + KVBLK <= Sk) && (!causal || (kv0 + KVBLK - 1 <= qb)) &&
              !seg_mask;
+    } else if constexpr (HAS_BAND) {
+      // band form: the tile against the band of the wave's 32 rows
+      active = ba_band_wave_active(qb, kv0, bd);
+      full = (kv0 + KVBLK <= Sk) && ba_band_wave_inside(qb, kv0, bd);
+      band_full = full;
     } else {
       active = !causal || (kv0 <= qb + 31);
     }
@@ -606,7 +665,7 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
       // the diagonal for every q row of this wave.  (SUBT=0 takes its own
       // copy after its QK MFMAs: reading this one costs its register-tight
       // tr16 kernels 4 to 8 bytes more scratch.)
-      if constexpr (!HAS_SEG)
+      if constexpr (!HAS_MASK)
         full = (kv0 + KVBLK <= Sk) && (!causal || (kv0 + KVBLK - 1 <= qb));
       if (SUBT == 3) {
         // NOTE: a C-level warmup peel (separate guarded/steady calls)
@@ -787,7 +846,7 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
     } else {
       // segment form: a row that saw no key has l = 0: o = 0, lse = -inf
       float inv_l = 1.f / lsum;
-      if constexpr (HAS_SEG) inv_l = lsum == 0.f ? 0.f : inv_l;
+      if constexpr (HAS_MASK) inv_l = lsum == 0.f ? 0.f : inv_l;
       float* orow = o + (((int64_t)b * Sq + q_row) * N + n) * D;
 #pragma unroll
       for (int dt = 0; dt < D / 32; ++dt)
@@ -827,6 +886,33 @@ __global__ void attn_fwd_finalize_kernel(
   if (sub == 0)
     lse[((int64_t)b * N + n) * S + s] =
         BA_LN2 * (m[((int64_t)b * N + n) * S + s] + log2f(lv));
+}
+
+// the empty carry-in state: acc = 0, l = 0, m = the level a carry_in = 0
+// call starts from.  One thread per V floats of acc (V = 4 where the state
+// is 16-byte aligned, else 1); the threads of d = 0 also write m and l.
+template <int V>
+__global__ __launch_bounds__(256) void attn_fwd_state_init_kernel(
+    float* __restrict__ acc, float* __restrict__ m, float* __restrict__ l,
+    int S, int N, int D, int64_t a_sb, int64_t a_ss, int64_t a_sh,
+    int64_t ml_sb, int64_t ml_sh) {
+  const int dv = D / V;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int b = blockIdx.y;
+  if (i >= (int64_t)S * N * dv) return;
+  const int d = (int)(i % dv) * V;
+  const int n = (int)((i / dv) % N);
+  const int s = (int)(i / ((int64_t)dv * N));
+  float* row = acc + b * a_sb + (int64_t)s * a_ss + n * a_sh + d;
+  if (V == 4) {
+    *(float4*)row = make_float4(0.f, 0.f, 0.f, 0.f);
+  } else {
+    row[0] = 0.f;
+  }
+  if (d == 0) {
+    m[b * ml_sb + n * ml_sh + s] = BA_NEG_BIG;
+    l[b * ml_sb + n * ml_sh + s] = 0.f;
+  }
 }
 
 // V^T image pre-pass (layout: vt_image.h).  One workgroup per (kv tile, kv
@@ -1038,9 +1124,9 @@ static int seg_ids_given(const void* q_seg, const void* kv_seg, int* given) {
 // kernel whatever BA_FWD_VT says (one kernel, so the results cannot depend
 // on that knob), never the module kernel.  Pre-pass, then the forward, on
 // the same stream.
-static int fwd_seg_entry(const fwd_args& a, const fwd_seg_call& sc,
-                         int out_state, int64_t B, int64_t Sq, int64_t Sk,
-                         int64_t D, int dtype, hipStream_t stream) {
+// Both masked forms (segment ids, band) exist for the default variant only:
+// 0 when the BA_FWD_* knobs select it, else the error naming the knob.
+static int fwd_default_variant_only(const char* what) {
   ba_fwd_knobs kn;
   kn.vpath = ba_env_int(BA_FWD_KNOB_SPECS[0].env, kn.vpath);
   kn.subt = ba_env_int(BA_FWD_KNOB_SPECS[1].env, kn.subt);
@@ -1054,9 +1140,15 @@ static int fwd_seg_entry(const fwd_args& a, const fwd_seg_call& sc,
   const ba_seg_verdict sv = ba_seg_fwd_support(kn);
   if (sv.knob)
     return ba_fail(BAHIP_ERR_UNSUPPORTED,
-                   "%s=%d does not support segment ids (default forward "
-                   "variant only)",
-                   sv.knob, sv.value);
+                   "%s=%d does not support %s (default forward variant only)",
+                   sv.knob, sv.value, what);
+  return 0;
+}
+
+static int fwd_seg_entry(const fwd_args& a, const fwd_seg_call& sc,
+                         int out_state, int64_t B, int64_t Sq, int64_t Sk,
+                         int64_t D, int dtype, hipStream_t stream) {
+  if (int rc = fwd_default_variant_only("segment ids")) return rc;
   if (B < 1 || B > 65535 || Sq < 1 || Sk < 1)
     return ba_fail(BAHIP_ERR_UNSUPPORTED,
                    "segment ids: unsupported shape B=%d Sq=%d Sk=%d", (int)B,
@@ -1094,6 +1186,61 @@ static int fwd_seg_entry(const fwd_args& a, const fwd_seg_call& sc,
     else
       go(attn_fwd_kernel<T, TD, 64, 0, P.vpath, P.subt, P.nt, P.nbuf, P.kreg,
                          0, ba_seg_args>);
+    return ba_launch_status();
+  });
+}
+
+// ---- band form ------------------------------------------------------------
+// What a *_band entry point adds to the plain call: the band as given.
+struct fwd_band_call {
+  int64_t lo, hi;
+};
+
+// The band a kernel gets: lo > hi is the caller's bug; causal cuts the band
+// at the diagonal (the band kernels never read `causal`); the bounds are
+// clamped so that no row difference can overflow against them.
+static int ba_band_for_kernel(int64_t lo, int64_t hi, int causal,
+                              ba_band_args* out) {
+  if (lo > hi)
+    return ba_fail(BAHIP_ERR_BAND, "band: lo=%lld is above hi=%lld",
+                   (long long)lo, (long long)hi);
+  if (causal && lo < 0) lo = 0;
+  out->lo = ba_band_clamp(lo);
+  out->hi = ba_band_clamp(hi);
+  return 0;
+}
+
+// The forward with a band: as with ids, the default variant only, V
+// transposed in the kernel (the V^T workspace is ignored), never the module
+// kernel.  No pre-pass: the kernel computes its tile range itself.
+static int fwd_band_entry(const fwd_args& a, const fwd_band_call& bc,
+                          int out_state, int64_t B, int64_t Sq, int64_t Sk,
+                          int64_t D, int dtype, hipStream_t stream) {
+  ba_band_args bd;
+  if (int rc = ba_band_for_kernel(bc.lo, bc.hi, a.causal, &bd)) return rc;
+  if (int rc = fwd_default_variant_only("a band")) return rc;
+  if (B < 1 || B > 65535 || Sq < 1 || Sk < 1)
+    return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                   "band: unsupported shape B=%d Sq=%d Sk=%d", (int)B, (int)Sq,
+                   (int)Sk);
+  return ba_dispatch_td(D, dtype, [&](auto td) {
+    using T = typename decltype(td)::type;
+    constexpr int TD = decltype(td)::D;
+    constexpr ba_fwd_variant P = BA_FWD_PRODUCTION;
+    const dim3 grid = fwd_grid(a, B, P.nt);
+    auto go = [&](auto kernel) {
+      kernel<<<grid, dim3(P.nt), 0, stream>>>(
+          (const T*)a.q, (const T*)a.k, (const T*)a.v, a.o, a.lse, a.Sq, a.Sk,
+          a.N, a.G, a.q_sb, a.q_ss, a.q_sh, a.k_sb, a.k_ss, a.k_sh, a.v_sb,
+          a.v_ss, a.v_sh, a.scale, a.causal, a.st_acc, a.st_m, a.st_l, a.a_sb,
+          a.a_ss, a.a_sh, a.ml_sb, a.ml_sh, a.carry_in, bd);
+    };
+    if (out_state)
+      go(attn_fwd_kernel<T, TD, 64, 1, P.vpath, P.subt, P.nt, P.nbuf, P.kreg,
+                         0, ba_band_args>);
+    else
+      go(attn_fwd_kernel<T, TD, 64, 0, P.vpath, P.subt, P.nt, P.nbuf, P.kreg,
+                         0, ba_band_args>);
     return ba_launch_status();
   });
 }
@@ -1165,7 +1312,8 @@ static int fwd_entry(void* hip_function, int out_state, const void* q,
                      float* acc, float* m,
                      float* l, const int64_t* as, const int64_t* mls,
                      int carry_in, void* ws, int64_t ws_bytes, void* stream,
-                     const fwd_seg_call* seg = nullptr) {
+                     const fwd_seg_call* seg = nullptr,
+                     const fwd_band_call* band = nullptr) {
   if (causal && Sq != Sk)
     return ba_fail(BAHIP_ERR_CAUSAL_SHAPE,
                    "causal tiles require Sq == Sk (%d vs %d)", (int)Sq,
@@ -1185,6 +1333,9 @@ static int fwd_entry(void* hip_function, int out_state, const void* q,
   if (seg)
     return fwd_seg_entry(a, *seg, out_state, B, Sq, Sk, D, dtype,
                          (hipStream_t)stream);
+  if (band)
+    return fwd_band_entry(a, *band, out_state, B, Sq, Sk, D, dtype,
+                          (hipStream_t)stream);
   if (hip_function) {
     if (D != 128 || (dtype != BAHIP_F16 && dtype != BAHIP_BF16))
       return ba_fail(BAHIP_ERR_UNSUPPORTED,
@@ -1317,6 +1468,57 @@ extern "C" int bahip_attn_fwd_accum_seg(
                    Nk, D, q_strides, k_strides, v_strides, softmax_scale,
                    causal, dtype, acc, m, l, acc_strides, ml_strides, carry_in,
                    workspace, workspace_bytes, stream, given ? &sc : nullptr);
+}
+
+extern "C" int bahip_attn_fwd_band(
+    const void* q, const void* k, const void* v, float* o, float* lse,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    int64_t band_lo, int64_t band_hi, void* stream) {
+  const fwd_band_call bc = {band_lo, band_hi};
+  return fwd_entry(nullptr, 0, q, k, v, o, lse, B, Sq, Sk, N, Nk, D, q_strides,
+                   k_strides, v_strides, softmax_scale, causal, dtype, nullptr,
+                   nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, stream,
+                   nullptr, &bc);
+}
+
+extern "C" int bahip_attn_fwd_accum_band(
+    void* hip_function, const void* q, const void* k, const void* v,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    float* acc, float* m, float* l, const int64_t acc_strides[3],
+    const int64_t ml_strides[2], int carry_in, int64_t band_lo,
+    int64_t band_hi, void* stream) {
+  const fwd_band_call bc = {band_lo, band_hi};
+  return fwd_entry(hip_function, 1, q, k, v, nullptr, nullptr, B, Sq, Sk, N,
+                   Nk, D, q_strides, k_strides, v_strides, softmax_scale,
+                   causal, dtype, acc, m, l, acc_strides, ml_strides, carry_in,
+                   nullptr, 0, stream, nullptr, &bc);
+}
+
+extern "C" int bahip_attn_fwd_state_init(
+    float* acc, float* m, float* l, int64_t B, int64_t S, int64_t N, int64_t D,
+    const int64_t acc_strides[3], const int64_t ml_strides[2], void* stream) {
+  if (B < 1 || B > 65535 || S < 1 || N < 1 || (D != 64 && D != 128))
+    return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                   "state init: unsupported shape B=%d S=%d N=%d D=%d", (int)B,
+                   (int)S, (int)N, (int)D);
+  const bool vec = (uintptr_t)acc % 16 == 0 && acc_strides[0] % 4 == 0 &&
+                   acc_strides[1] % 4 == 0 && acc_strides[2] % 4 == 0;
+  const int64_t threads = S * N * (vec ? D / 4 : D);
+  const dim3 grid((unsigned)((threads + 255) / 256), (unsigned)B);
+  auto go = [&](auto kernel) {
+    kernel<<<grid, 256, 0, (hipStream_t)stream>>>(
+        acc, m, l, (int)S, (int)N, (int)D, acc_strides[0], acc_strides[1],
+        acc_strides[2], ml_strides[0], ml_strides[1]);
+  };
+  if (vec)
+    go(attn_fwd_state_init_kernel<4>);
+  else
+    go(attn_fwd_state_init_kernel<1>);
+  return ba_launch_status();
 }
 
 extern "C" int64_t bahip_attn_seg_workspace_bytes(int64_t B, int64_t Sq,

@@ -123,6 +123,18 @@ SegIds seg_ids(const c10::optional<at::Tensor>& q_seg,
   return s;
 }
 
+// The band of a call: band_lo and band_hi together or not at all, and never
+// together with segment ids (that combination has no kernel form yet).
+bool band_given(const c10::optional<int64_t>& band_lo,
+                const c10::optional<int64_t>& band_hi, const SegIds& seg) {
+  TORCH_CHECK(band_lo.has_value() == band_hi.has_value(),
+              "band_lo and band_hi must be given together");
+  TORCH_CHECK(!(band_lo.has_value() && seg.q),
+              "band_lo/band_hi and q_seg/kv_seg are not supported together "
+              "yet");
+  return band_lo.has_value();
+}
+
 // The pre-pass alone on [B, Sq] / [B, Sk] ids: the workspace as int32
 // words (layout: bahip_attn_seg_prepass).  For tests and measurements.
 at::Tensor attn_seg_prepass(const at::Tensor& q_seg, const at::Tensor& kv_seg) {
@@ -148,13 +160,24 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k,
                                  const at::Tensor& v, double softmax_scale,
                                  bool causal,
                                  const c10::optional<at::Tensor>& q_seg,
-                                 const c10::optional<at::Tensor>& kv_seg) {
+                                 const c10::optional<at::Tensor>& kv_seg,
+                                 const c10::optional<int64_t>& band_lo,
+                                 const c10::optional<int64_t>& band_hi) {
   check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
   const SegIds seg = seg_ids(q_seg, kv_seg, q, k);
   auto o = at::empty({B, Sq, N, D}, q.options().dtype(at::kFloat));
   auto lse = at::empty({B, N, Sq}, q.options().dtype(at::kFloat));
+  if (band_given(band_lo, band_hi, seg)) {
+    BA_CALL(bahip_attn_fwd_band(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr<float>(),
+        lse.data_ptr<float>(), B, Sq, Sk, N, k.size(2), D, Strides3(q),
+        Strides3(k), Strides3(v), (float)softmax_scale, causal ? 1 : 0,
+        dtype_code(q), *band_lo, *band_hi,
+        at::hip::getCurrentHIPStream().stream()));
+    return {o, lse};
+  }
   // with ids the forward transposes V in the kernel: no image workspace
   auto ws = seg.q ? at::Tensor() : fwd_workspace(q, k);
   auto stream = at::hip::getCurrentHIPStream().stream();
@@ -206,7 +229,9 @@ void fwd_accum_call(void* asm_fn, const at::Tensor& q, const at::Tensor& k,
                     at::Tensor& acc, at::Tensor& m, at::Tensor& l,
                     bool carry_in,
                     const c10::optional<at::Tensor>& q_seg = c10::nullopt,
-                    const c10::optional<at::Tensor>& kv_seg = c10::nullopt) {
+                    const c10::optional<at::Tensor>& kv_seg = c10::nullopt,
+                    const c10::optional<int64_t>& band_lo = c10::nullopt,
+                    const c10::optional<int64_t>& band_hi = c10::nullopt) {
   check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
@@ -220,6 +245,16 @@ void fwd_accum_call(void* asm_fn, const at::Tensor& q, const at::Tensor& k,
   int64_t mls[2] = {m.stride(0), m.stride(1)};
   TORCH_CHECK(l.stride(0) == mls[0] && l.stride(1) == mls[1],
               "m/l stride mismatch");
+  if (band_given(band_lo, band_hi, seg)) {
+    BA_CALL(bahip_attn_fwd_accum_band(
+        nullptr, q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Sq, Sk, N,
+        k.size(2), D, Strides3(q), Strides3(k), Strides3(v),
+        (float)softmax_scale, causal ? 1 : 0, dtype_code(q),
+        acc.data_ptr<float>(), m.data_ptr<float>(), l.data_ptr<float>(),
+        Strides3(acc), mls, carry_in ? 1 : 0, *band_lo, *band_hi,
+        at::hip::getCurrentHIPStream().stream()));
+    return;
+  }
   // the module kernel and the segment form transpose V themselves: no
   // image workspace
   auto ws = (asm_fn || seg.q) ? at::Tensor() : fwd_workspace(q, k);
@@ -238,9 +273,32 @@ void attn_fwd_accum(const at::Tensor& q, const at::Tensor& k,
                     const at::Tensor& v, double softmax_scale, bool causal,
                     at::Tensor& acc, at::Tensor& m, at::Tensor& l,
                     bool carry_in, const c10::optional<at::Tensor>& q_seg,
-                    const c10::optional<at::Tensor>& kv_seg) {
+                    const c10::optional<at::Tensor>& kv_seg,
+                    const c10::optional<int64_t>& band_lo,
+                    const c10::optional<int64_t>& band_hi) {
   fwd_accum_call(nullptr, q, k, v, softmax_scale, causal, acc, m, l, carry_in,
-                 q_seg, kv_seg);
+                 q_seg, kv_seg, band_lo, band_hi);
+}
+
+// The empty carry-in state ("no key seen yet") written into acc [B,S,N,D],
+// m and l [B,N,S] (fp32, strided views allowed as in attn_fwd_accum).
+void attn_fwd_state_init(at::Tensor& acc, at::Tensor& m, at::Tensor& l) {
+  TORCH_CHECK(acc.is_cuda() && m.is_cuda() && l.is_cuda() && acc.dim() == 4 &&
+                  m.dim() == 3 && l.dim() == 3,
+              "state must be GPU tensors acc [B,S,N,D], m/l [B,N,S]");
+  TORCH_CHECK(acc.scalar_type() == at::kFloat && m.scalar_type() == at::kFloat
+                  && l.scalar_type() == at::kFloat, "state must be fp32");
+  const auto B = acc.size(0), S = acc.size(1), N = acc.size(2), D = acc.size(3);
+  TORCH_CHECK(m.sizes() == at::IntArrayRef({B, N, S}) && l.sizes() == m.sizes(),
+              "m/l must be [B,N,S] of acc's [B,S,N,D]");
+  TORCH_CHECK(acc.stride(3) == 1 && m.stride(2) == 1 && l.stride(2) == 1,
+              "state innermost dims must be contiguous");
+  int64_t mls[2] = {m.stride(0), m.stride(1)};
+  TORCH_CHECK(l.stride(0) == mls[0] && l.stride(1) == mls[1],
+              "m/l stride mismatch");
+  BA_CALL(bahip_attn_fwd_state_init(
+      acc.data_ptr<float>(), m.data_ptr<float>(), l.data_ptr<float>(), B, S, N,
+      D, Strides3(acc), mls, at::hip::getCurrentHIPStream().stream()));
 }
 
 std::vector<at::Tensor> attn_fwd_finalize(const at::Tensor& acc,
@@ -301,7 +359,9 @@ void attn_bwd_accum(const at::Tensor& dout, const at::Tensor& q,
                     double softmax_scale, bool causal, bool deterministic,
                     at::Tensor& dq, at::Tensor& dk, at::Tensor& dv,
                     const c10::optional<at::Tensor>& q_seg,
-                    const c10::optional<at::Tensor>& kv_seg) {
+                    const c10::optional<at::Tensor>& kv_seg,
+                    const c10::optional<int64_t>& band_lo,
+                    const c10::optional<int64_t>& band_hi) {
   check_qkv(dout, "dout");
   check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
@@ -324,6 +384,17 @@ void attn_bwd_accum(const at::Tensor& dout, const at::Tensor& q,
   int64_t ds[2] = {delta.stride(0), delta.stride(1)};
   int64_t ls[2] = {lse.stride(0), lse.stride(1)};
   auto stream = at::hip::getCurrentHIPStream().stream();
+  if (band_given(band_lo, band_hi, seg)) {
+    BA_CALL(bahip_attn_bwd_band(
+        dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+        delta.data_ptr<float>(), lse.data_ptr<float>(), dq.data_ptr<float>(),
+        dk.data_ptr<float>(), dv.data_ptr<float>(), B, Sq, Sk, N, k.size(2), D,
+        Strides3(dout), Strides3(q), Strides3(k), Strides3(v), ds, ls,
+        Strides3(dq), Strides3(dk), Strides3(dv), (float)softmax_scale,
+        causal ? 1 : 0, deterministic ? 1 : 0, dtype_code(q), *band_lo,
+        *band_hi, stream));
+    return;
+  }
   BA_CALL(bahip_attn_bwd_seg(
       dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
       delta.data_ptr<float>(), lse.data_ptr<float>(), dq.data_ptr<float>(),
@@ -340,7 +411,9 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
                                  const at::Tensor& lse, double softmax_scale,
                                  bool causal, bool deterministic,
                                  const c10::optional<at::Tensor>& q_seg,
-                                 const c10::optional<at::Tensor>& kv_seg) {
+                                 const c10::optional<at::Tensor>& kv_seg,
+                                 const c10::optional<int64_t>& band_lo,
+                                 const c10::optional<int64_t>& band_hi) {
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
   // zero-filled: the kernels accumulate, so this equals fresh outputs
@@ -350,7 +423,7 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
   auto dk = at::zeros({B, Sk, Nk, D}, q.options().dtype(at::kFloat));
   auto dv = at::zeros({B, Sk, Nk, D}, q.options().dtype(at::kFloat));
   attn_bwd_accum(dout, q, k, v, delta, lse, softmax_scale, causal,
-                 deterministic, dq, dk, dv, q_seg, kv_seg);
+                 deterministic, dq, dk, dv, q_seg, kv_seg, band_lo, band_hi);
   return {dq, dk, dv};
 }
 
@@ -416,13 +489,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd", &attn_fwd, "BurstAttention fwd tile (gfx950)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("softmax_scale"),
         py::arg("causal"), py::arg("q_seg") = py::none(),
-        py::arg("kv_seg") = py::none());
+        py::arg("kv_seg") = py::none(), py::arg("band_lo") = py::none(),
+        py::arg("band_hi") = py::none());
   m.def("attn_fwd_accum", &attn_fwd_accum,
         "carry-in accumulator fwd tile (in-kernel LSE merge)", py::arg("q"),
         py::arg("k"), py::arg("v"), py::arg("softmax_scale"),
         py::arg("causal"), py::arg("acc"), py::arg("m"), py::arg("l"),
         py::arg("carry_in"), py::arg("q_seg") = py::none(),
-        py::arg("kv_seg") = py::none());
+        py::arg("kv_seg") = py::none(), py::arg("band_lo") = py::none(),
+        py::arg("band_hi") = py::none());
+  m.def("attn_fwd_state_init", &attn_fwd_state_init,
+        "write the empty carry-in state (no key seen yet) into acc, m, l");
   m.def("attn_seg_prepass", &attn_seg_prepass,
         "segment-id pre-pass alone: the int32 workspace (tile summaries and "
         "block ranges of both side pairs)");
@@ -442,13 +519,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("delta"), py::arg("lse"), py::arg("softmax_scale"),
         py::arg("causal"), py::arg("deterministic"),
-        py::arg("q_seg") = py::none(), py::arg("kv_seg") = py::none());
+        py::arg("q_seg") = py::none(), py::arg("kv_seg") = py::none(),
+        py::arg("band_lo") = py::none(), py::arg("band_hi") = py::none());
   m.def("attn_bwd_accum", &attn_bwd_accum,
         "bwd tile accumulating into fp32 dq/dk/dv views", py::arg("dout"),
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("delta"),
         py::arg("lse"), py::arg("softmax_scale"), py::arg("causal"),
         py::arg("deterministic"), py::arg("dq"), py::arg("dk"), py::arg("dv"),
-        py::arg("q_seg") = py::none(), py::arg("kv_seg") = py::none());
+        py::arg("q_seg") = py::none(), py::arg("kv_seg") = py::none(),
+        py::arg("band_lo") = py::none(), py::arg("band_hi") = py::none());
   m.def("mfma_probe", &mfma_probe, "32x32x16 MFMA layout probe");
   m.def("tr16_probe", &tr16_probe, "ds_read_tr16_b64 semantics probe");
   m.def("attn_fwd_asm_load", &attn_fwd_asm_load,

@@ -38,6 +38,17 @@ compared for equality only, so they need nothing from ``tile_window`` and
 the causal flag of a tile keeps its meaning.  Without ``segment_ids``
 neither the payloads nor the provider calls change.
 
+Sliding windows: the trailing keyword ``window_size=(left, right)`` (the
+flash-attn convention: the query at GLOBAL position i sees the key at global
+position j iff ``i - left <= j <= i + right``, -1 = unbounded, ``causal``
+forces ``right = 0``).  The global position of a local row follows from the
+op's data layout (zigzag for ``burst_attn_func`` with ``causal``, contiguous
+without, striped for ``burst_attn_func_striped``); ``window_tiles`` turns a
+round into sub-tiles, each a plain, causal or ``band=(lo, hi)`` call of the
+tile provider, and a round with no visible pair computes nothing (its
+communication is unchanged).  Without a window neither the provider calls
+nor the kernels change.  A window together with ``segment_ids`` is refused.
+
 The two causal load-balancing layouts (see oracle/partition.py) run the
 same code: ``OpBurstAttn`` (zigzag: rank r holds global chunks [r] and
 [2W-1-r]) and ``OpBurstAttnStrip`` (striped: token t on rank t mod W) only
@@ -59,7 +70,8 @@ from .tile import get_tile_provider
 
 _logger = get_logger(__name__, level="WARN")
 
-__all__ = ["burst_attn_func", "burst_attn_func_striped", "OpBurstAttn", "OpBurstAttnStrip"]
+__all__ = ["burst_attn_func", "burst_attn_func_striped", "OpBurstAttn",
+           "OpBurstAttnStrip", "window_tiles"]
 
 
 def get_partition_id(double_group, r, process_group=None):
@@ -108,6 +120,86 @@ def tile_window(layout, a, b, causal, s_local):
     # :322-345)
     half = s_local // 2
     return (_ALL, slice(None, half), False) if b < a else (slice(half, None), _ALL, False)
+
+
+# an unbounded side of a band, as a bound the tile provider accepts (the
+# launchers clamp far below it)
+BAND_INF = 1 << 40
+
+
+def _pieces(layout, rank, W, s_local):
+    """The runs of a rank's local rows that are arithmetic in the global
+    position: ``(local_start, rows, global_start, stride)``."""
+    if layout == "zigzag":
+        assert s_local % 2 == 0, (
+            "zigzag needs an even per-rank seqlen (the rank holds two "
+            "half-chunks)"
+        )
+        h = s_local // 2
+        return [(0, h, rank * h, 1), (h, h, (2 * W - 1 - rank) * h, 1)]
+    if layout == "contiguous":
+        return [(0, s_local, rank * s_local, 1)]
+    if layout == "striped":
+        return [(0, s_local, rank, W)]
+    raise ValueError(f"unknown layout {layout!r}")
+
+
+def window_tiles(layout, a, b, W, s_local, causal, window):
+    """The sub-tiles that one ring round computes of the q chunk owned by
+    rank ``a`` against the kv chunk owned by rank ``b`` under the window
+    ``(left, right)`` on global positions: a list of ``(q_rows, kv_rows,
+    band_or_None, tile_causal)``, two slices of the ``s_local`` local rows,
+    the band ``(lo, hi)`` on the row indices of those two views (visible iff
+    ``lo <= i - j <= hi``) and the causal flag of the tile call.
+
+    Every (q piece, kv piece) pair of the two ranks (``_pieces``) has a band
+    in piece-local indices: with global starts Pq, Pk and unit stride,
+    ``i - j`` must lie in ``[-R - (Pq - Pk), L - (Pq - Pk)]``; with stride W
+    (striped) in ``[ceil((-R - (a - b)) / W), floor((L - (a - b)) / W)]``.
+    The pair is trimmed to the rows that see and the keys that are seen, the
+    band re-based to the trimmed views, and dropped if nothing is left.  A
+    band that covers its whole rectangle becomes a plain call, one that is
+    the causal triangle of a square a causal call: both run the kernels a
+    ring without a window runs."""
+    left, right = window
+    L = None if left < 0 else left
+    R = 0 if causal else (None if right < 0 else right)
+    out = []
+    for lq, nq, Pq, stride in _pieces(layout, a, W, s_local):
+        for lk, nk, Pk, _ in _pieces(layout, b, W, s_local):
+            if stride == 1:
+                lo = None if R is None else -R - (Pq - Pk)
+                hi = None if L is None else L - (Pq - Pk)
+            else:
+                lo = None if R is None else -((R + (Pq - Pk)) // stride)
+                hi = None if L is None else (L - (Pq - Pk)) // stride
+            if lo is not None and hi is not None and lo > hi:
+                continue  # striped: no multiple of W inside the window
+            # hull: q rows that see a key, keys that are seen
+            q0 = 0 if lo is None else max(0, lo)
+            q1 = nq - 1 if hi is None else min(nq - 1, hi + nk - 1)
+            k0 = 0 if hi is None else max(0, -hi)
+            k1 = nk - 1 if lo is None else min(nk - 1, nq - 1 - lo)
+            if q0 > q1 or k0 > k1:
+                continue
+            nq2, nk2 = q1 - q0 + 1, k1 - k0 + 1
+            lo2 = -BAND_INF if lo is None else lo - (q0 - k0)
+            hi2 = BAND_INF if hi is None else hi - (q0 - k0)
+            q_rows = slice(lq + q0, lq + q1 + 1)
+            kv_rows = slice(lk + k0, lk + k1 + 1)
+            if lo2 <= -(nk2 - 1) and hi2 >= nq2 - 1:
+                out.append((q_rows, kv_rows, None, False))
+            elif nq2 == nk2 and lo2 == 0 and hi2 >= nq2 - 1:
+                out.append((q_rows, kv_rows, None, True))
+            else:
+                out.append((q_rows, kv_rows, (lo2, hi2), False))
+    return out
+
+
+def _window_layout(layout, causal):
+    """The data layout a window's global positions follow: the zigzag op
+    holds contiguous chunks when it is not causal."""
+    return "contiguous" if layout == "zigzag" and not causal else layout
 
 
 def _record_stream(*tensors):
@@ -198,6 +290,28 @@ def _check_segment_ids(segment_ids, q):
     return segment_ids.to(torch.int32).contiguous()
 
 
+def _check_window(window_size, causal, segment_ids):
+    """None for "no window", else ``(left, right)`` as given."""
+    if window_size is None:
+        return None
+    if (not isinstance(window_size, (tuple, list)) or len(window_size) != 2
+            or any(isinstance(x, bool) or not isinstance(x, int)
+                   for x in window_size)
+            or any(x < -1 for x in window_size)):
+        raise ValueError(
+            "window_size must be a pair (left, right) of Python ints >= -1 "
+            f"(-1 = unbounded), got {window_size!r}"
+        )
+    left, right = window_size
+    if left == -1 and (causal or right == -1):
+        return None  # nothing bounded beyond what causal already does
+    if segment_ids is not None:
+        raise ValueError(
+            "window_size and segment_ids are not supported together yet"
+        )
+    return (left, right)
+
+
 def burst_attn_func(
     q: torch.Tensor,
     k: torch.Tensor,
@@ -211,12 +325,15 @@ def burst_attn_func(
     double_group=[None, None],
     *,
     segment_ids: torch.Tensor = None,
+    window_size=None,
 ):
     _check_heads(q, k, v)
+    window = _check_window(window_size, causal, segment_ids)
     return OpBurstAttn.apply(
         q, k, v, softmax_scale, flash, causal, optimize_bwd_comm,
         deterministic, process_group, double_group,
         _check_segment_ids(segment_ids, q),
+        *(() if window is None else (window,)),
     )
 
 
@@ -233,23 +350,28 @@ def burst_attn_func_striped(
     double_group=[None, None],
     *,
     segment_ids: torch.Tensor = None,
+    window_size=None,
 ):
     _check_heads(q, k, v)
+    window = _check_window(window_size, causal, segment_ids)
     return OpBurstAttnStrip.apply(
         q, k, v, softmax_scale, flash, causal, optimize_bwd_comm,
         deterministic, process_group, double_group,
         _check_segment_ids(segment_ids, q),
+        *(() if window is None else (window,)),
     )
 
 
 def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
                   causal=False, optimize_bwd_comm=False, deterministic=False,
                   process_group=None, double_group=[None, None],
-                  segment_ids=None):
+                  segment_ids=None, window=None):
     """Forward of both layouts: q stays, {k, v} travel the ring (with the
-    kv ids, when there are segment ids)."""
+    kv ids, when there are segment ids).  With a window every round is the
+    sub-tiles of ``window_tiles``, merged into a state that starts empty."""
     _check_flash_arg(flash)
     ctx.segment_ids = ids = segment_ids
+    ctx.window = window
     ctx.dq_group = double_group
     if isinstance(double_group[0], tuple):
         # [(group, dq_group), (group2, dq_group2)] — separate backward dq
@@ -275,18 +397,30 @@ def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
         kv_ids = replicate(ids)
         comm_bufs.append(torch.empty_like(ids))
     state = None  # provider-owned carry-in accumulator (in-kernel merge)
+    if window is not None:
+        state = P.fwd_empty_state(q)
+        wlayout = _window_layout(layout, causal)
     record = []
     for r in range(1, W + 1):
         src = get_partition_id(double_group, r, process_group)
         record.append(src)
-        qw, kw, tile_causal = tile_window(layout, rank, src, causal, q.shape[1])
+        if window is None:
+            qw, kw, tile_causal = tile_window(layout, rank, src, causal, q.shape[1])
         payload = [k, v] if ids is None else [k, v, kv_ids]
         if r != W:
             ring.double_ring_send_recv(payload, comm_bufs, r)
             ring.commit()
-        seg = {} if ids is None else {"seg": (ids[:, qw], kv_ids[:, kw])}
-        state = P.fwd_accum(state, q[:, qw], k[:, kw], v[:, kw], scale,
-                            tile_causal, row_offset=qw.start or 0, **seg)
+        if window is not None:
+            for qw, kw, band, tile_causal in window_tiles(
+                    wlayout, rank, src, W, q.shape[1], causal, window):
+                state = P.fwd_accum(
+                    state, q[:, qw], k[:, kw], v[:, kw], scale, tile_causal,
+                    row_offset=qw.start,
+                    **({} if band is None else {"band": band}))
+        else:
+            seg = {} if ids is None else {"seg": (ids[:, qw], kv_ids[:, kw])}
+            state = P.fwd_accum(state, q[:, qw], k[:, kw], v[:, kw], scale,
+                                tile_causal, row_offset=qw.start or 0, **seg)
         if r != W:
             recv, comm_bufs = _record_stream(*comm_bufs), payload
             k, v = recv[:2]
@@ -343,6 +477,7 @@ def _ring_backward(layout, ctx, grad_output):
     # travels with q as the q side
     ids = ctx.segment_ids
     q_ids = None if ids is None else replicate(ids)
+    window = ctx.window
     P = get_tile_provider()
     scale, causal = ctx.softmax_scale, ctx.causal
     grad_output = grad_output.contiguous()
@@ -375,7 +510,8 @@ def _ring_backward(layout, ctx, grad_output):
         read_bufs.append(torch.empty_like(q_ids))
     for r in range(1, W + 1):
         src = get_partition_id(double_group, r, group)
-        qw, kw, tile_causal = tile_window(layout, src, rank, causal, q.shape[1])
+        if window is None:
+            qw, kw, tile_causal = tile_window(layout, src, rank, causal, q.shape[1])
         payload = [dlt, grad_output, q, lse]
         if ids is not None:
             payload.append(q_ids)
@@ -389,12 +525,27 @@ def _ring_backward(layout, ctx, grad_output):
             else P.bwd_preprocess(dlt, grad_output, out=delta_buf)
         )
         tgt = dq if r == 1 else dq_local
-        P.bwd_accum(
-            grad_output[:, qw], q[:, qw], k[:, kw], v[:, kw],
-            delta[:, :, qw], lse[:, :, qw], scale, tile_causal,
-            ctx.deterministic, tgt[:, qw], dk[:, kw], dv[:, kw],
-            **({} if ids is None else {"seg": (q_ids[:, qw], ids[:, kw])}),
-        )
+        if window is not None:
+            tiles = window_tiles(_window_layout(layout, causal), src, rank, W,
+                                 q.shape[1], causal, window)
+            for qr, kr, band, tile_causal in tiles:
+                P.bwd_accum(
+                    grad_output[:, qr], q[:, qr], k[:, kr], v[:, kr],
+                    delta[:, :, qr], lse[:, :, qr], scale, tile_causal,
+                    ctx.deterministic, tgt[:, qr], dk[:, kr], dv[:, kr],
+                    **({} if band is None else {"band": band}),
+                )
+            # the dq fold below covers the union of the round's q rows (an
+            # empty slice when the round computed nothing)
+            qw = slice(min((t[0].start for t in tiles), default=0),
+                       max((t[0].stop for t in tiles), default=0))
+        else:
+            P.bwd_accum(
+                grad_output[:, qw], q[:, qw], k[:, kw], v[:, kw],
+                delta[:, :, qw], lse[:, :, qw], scale, tile_causal,
+                ctx.deterministic, tgt[:, qw], dk[:, kw], dv[:, kw],
+                **({} if ids is None else {"seg": (q_ids[:, qw], ids[:, kw])}),
+            )
         if r != W:
             recv, read_bufs = _record_stream(*read_bufs), payload
             dlt, grad_output, q, lse = recv[:4]
@@ -412,6 +563,7 @@ def _ring_backward(layout, ctx, grad_output):
     return (
         dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype),
         None, None, None, None, None, None, None, None,
+        *(() if window is None else (None,)),
     )
 
 

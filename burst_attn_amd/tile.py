@@ -49,6 +49,22 @@ windowed q and k/v.  A row that sees no key gives ``o = 0``, ``lse = -inf``
 and zero gradients.  A caller without ids passes no ``seg`` keyword at all,
 so a provider that predates it keeps working for id-free calls.
 
+Bands (sliding windows): the same four methods take an optional keyword
+``band=(lo, hi)``, two Python ints.  Pair (q row i, kv row j) *of the
+tensors passed* is then visible iff ``lo <= i - j <= hi``.  Rectangular
+tiles (``Sq != Sk``) are allowed, ``lo`` may be negative and either bound
+may be huge.  With ``causal=True`` the band is cut at the diagonal
+(``lo = max(lo, 0)``) and ``Sq == Sk`` is still demanded.  ``lo > hi`` is a
+caller bug and an error.  A row that sees no key behaves as with ids: the
+stateless forward gives ``o = 0``, ``lse = -inf``, a carry-in call leaves the
+row's state untouched, the backward adds exactly zero from and to it.
+``band`` and ``seg`` together are refused.  A caller without a band passes
+no ``band`` keyword at all.  ``fwd_empty_state(q)`` returns the carry-in
+state of "no key seen yet" over the rank's full ``[B, S, N, D]`` q:
+finalizing it gives ``o = 0``, ``lse = -inf``, and ``fwd_accum`` merges into
+it at any ``row_offset``; a ring whose first tile does not cover every row
+starts from it.
+
 The default provider is the gfx950 HIP extension and FAILS LOUDLY if the
 extension is missing on a GPU machine — there is no CPU/eager fallback in
 the product path.  Tests may inject an oracle-backed provider via
@@ -97,28 +113,37 @@ class HipTileProvider:
                                         syms["bf16_accum"])
             self._asm_fwd = True
 
-    def fwd(self, q, k, v, scale, causal, seg=None):
+    @staticmethod
+    def _band_kw(band):
+        """The extension's keywords of a ``band=(lo, hi)``; none without."""
+        if band is None:
+            return {}
+        lo, hi = band
+        return {"band_lo": int(lo), "band_hi": int(hi)}
+
+    def fwd(self, q, k, v, scale, causal, seg=None, band=None):
         q_seg, kv_seg = seg if seg is not None else (None, None)
         return self._ext.attn_fwd(q, k, v, float(scale), bool(causal),
-                                  q_seg, kv_seg)
+                                  q_seg, kv_seg, **self._band_kw(band))
 
     def bwd_preprocess(self, o, do, out=None):
         return self._ext.attn_bwd_preprocess(o, do, out)
 
     def bwd(self, do, q, k, v, delta, lse, scale, causal, deterministic,
-            seg=None):
+            seg=None, band=None):
         q_seg, kv_seg = seg if seg is not None else (None, None)
         return self._ext.attn_bwd(
             do, q, k, v, delta, lse, float(scale), bool(causal),
-            bool(deterministic), q_seg, kv_seg,
+            bool(deterministic), q_seg, kv_seg, **self._band_kw(band),
         )
 
     def bwd_accum(self, do, q, k, v, delta, lse, scale, causal, deterministic,
-                  dq, dk, dv, seg=None):
+                  dq, dk, dv, seg=None, band=None):
         q_seg, kv_seg = seg if seg is not None else (None, None)
         self._ext.attn_bwd_accum(
             do, q, k, v, delta, lse, float(scale), bool(causal),
             bool(deterministic), dq, dk, dv, q_seg, kv_seg,
+            **self._band_kw(band),
         )
 
     def merge(self, o, lse, o_i, lse_i):
@@ -128,14 +153,18 @@ class HipTileProvider:
     # state = (acc fp32 [B,S,N,D] unnormalised O, m fp32 [B,N,S] exp2-domain
     # running max, l fp32 [B,N,S] running sum) over the rank's FULL chunk;
     # row_offset targets the zigzag-half / striped-shift row windows.
-    def fwd_accum(self, state, q, k, v, scale, causal, row_offset=0, seg=None):
+    def fwd_accum(self, state, q, k, v, scale, causal, row_offset=0, seg=None,
+                  band=None):
         # the .s-built module carries the D=128 production variants only,
-        # and no segment form: with ids the in-binary kernel runs
-        if self._asm_fwd and q.shape[3] == 128 and seg is None:
+        # and no segment or band form: with either the in-binary kernel runs
+        if (self._asm_fwd and q.shape[3] == 128 and seg is None
+                and band is None):
             accum = self._ext.attn_fwd_accum_asm
-        elif seg is not None:
+        elif seg is not None or band is not None:
+            q_seg, kv_seg = seg if seg is not None else (None, None)
             accum = functools.partial(self._ext.attn_fwd_accum,
-                                      q_seg=seg[0], kv_seg=seg[1])
+                                      q_seg=q_seg, kv_seg=kv_seg,
+                                      **self._band_kw(band))
         else:
             accum = self._ext.attn_fwd_accum
         if state is None:
@@ -152,6 +181,15 @@ class HipTileProvider:
         accv, mv, lv = acc[:, sl], m[:, :, sl], l[:, :, sl]
         accum(q, k, v, float(scale), bool(causal), accv, mv, lv, True)
         return state
+
+    def fwd_empty_state(self, q):
+        """The state of "no key seen yet" over q's [B, S, N, D] rows."""
+        B, S, N, D = q.shape
+        acc = torch.empty(B, S, N, D, dtype=torch.float32, device=q.device)
+        m = torch.empty(B, N, S, dtype=torch.float32, device=q.device)
+        l = torch.empty(B, N, S, dtype=torch.float32, device=q.device)
+        self._ext.attn_fwd_state_init(acc, m, l)
+        return (acc, m, l)
 
     def fwd_finalize(self, state, out_dtype):
         acc, m, l = state

@@ -71,6 +71,23 @@
  *     BAHIP_ERR_UNSUPPORTED naming the knob, and nothing is launched.  The
  *     forward with ids transposes V in the kernel whatever BA_FWD_VT says
  *     (its V^T workspace argument is ignored) and never uses hip_function.
+ *   - band (sliding windows): the *_band entry points take band_lo and
+ *     band_hi.  Pair (q row i, kv row j) of the tensors passed is visible iff
+ *     band_lo <= i - j <= band_hi; Sq != Sk is allowed, band_lo may be
+ *     negative and either bound may be huge (they are clamped to +-2^30).
+ *     With causal the band is cut at the diagonal, band_lo = max(band_lo, 0),
+ *     and Sq == Sk is still demanded.  band_lo > band_hi returns
+ *     BAHIP_ERR_BAND and launches nothing.  There is no pre-pass and no
+ *     workspace: a workgroup computes the range of 64-row tiles that can hold
+ *     a visible pair from its block index, the band and the two lengths, and
+ *     a wave skips a tile that misses the band of its 32 rows.  A row that
+ *     sees no key behaves exactly as with segment ids (o = 0, lse = -inf; an
+ *     untouched carry-in state; exactly zero gradients).  A band is supported
+ *     where segment ids are: another BA_FWD_* variant, BA_BWD_FUSED=1/2,
+ *     BA_BWD_DK_FLIP=1 or BA_DQ_PIPE=1 returns BAHIP_ERR_UNSUPPORTED naming
+ *     the knob, V is transposed in the kernel, and a module kernel
+ *     (hip_function) is never used.  A band together with segment ids has no
+ *     entry point.
  *   - stream is a hipStream_t.
  * Returns 0 on success; nonzero = error.  Every nonzero return sets the
  * calling thread's bahip_last_error() message and every success clears it.
@@ -98,6 +115,8 @@ extern "C" {
                                          small; nothing is launched */
 
 #define BAHIP_ERR_SEGMENT_IDS 1006    /* one of q_seg / kv_seg is null */
+
+#define BAHIP_ERR_BAND 1007           /* band_lo > band_hi */
 
 const char* bahip_last_error(void);
 
@@ -305,6 +324,52 @@ int bahip_attn_bwd_seg(
     const int32_t* q_seg, const int32_t* kv_seg,
     int64_t q_seg_stride, int64_t kv_seg_stride,
     void* seg_workspace, int64_t seg_workspace_bytes, void* stream);
+
+/* ---- band (see "band" above) -------------------------------------------
+ * bahip_attn_fwd_gqa, bahip_attn_fwd_accum_gqa and bahip_attn_bwd_gqa with a
+ * band on the row indices of the tensors passed.  hip_function is accepted
+ * for the signature's sake and ignored. */
+int bahip_attn_fwd_band(
+    const void* q, const void* k, const void* v,
+    float* o, float* lse,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3],
+    const int64_t k_strides[3],
+    const int64_t v_strides[3],
+    float softmax_scale, int causal, int dtype,
+    int64_t band_lo, int64_t band_hi, void* stream);
+int bahip_attn_fwd_accum_band(
+    void* hip_function,
+    const void* q, const void* k, const void* v,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    float* acc, float* m, float* l, const int64_t acc_strides[3],
+    const int64_t ml_strides[2], int carry_in,
+    int64_t band_lo, int64_t band_hi, void* stream);
+int bahip_attn_bwd_band(
+    const void* dout, const void* q, const void* k, const void* v,
+    const float* delta, const float* lse,
+    float* dq, float* dk, float* dv,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t do_strides[3], const int64_t q_strides[3],
+    const int64_t k_strides[3], const int64_t v_strides[3],
+    const int64_t delta_strides[2], const int64_t lse_strides[2],
+    const int64_t dq_strides[3], const int64_t dk_strides[3],
+    const int64_t dv_strides[3],
+    float softmax_scale, int causal, int deterministic, int dtype,
+    int64_t band_lo, int64_t band_hi, void* stream);
+
+/* The empty state, "no key seen yet", over [B, S] rows of a carry-in state
+ * (acc strided {b,s,h}, m/l strided {b,h}, as in bahip_attn_fwd_accum):
+ * acc = 0, l = 0 and the m a carry_in = 0 call starts from.
+ * bahip_attn_fwd_finalize of it gives o = 0, lse = -inf, and a later
+ * carry_in = 1 call merges into it exactly as a carry_in = 0 call would have
+ * initialised it. */
+int bahip_attn_fwd_state_init(
+    float* acc, float* m, float* l,
+    int64_t B, int64_t S, int64_t N, int64_t D,
+    const int64_t acc_strides[3], const int64_t ml_strides[2], void* stream);
 
 #ifdef __cplusplus
 }
