@@ -349,6 +349,8 @@ def main():
     p.add_argument("--dtype", choices=["fp16", "bf16"], default="fp16")
     p.add_argument("--out", default="results_mi355x.jsonl")
     p.add_argument("--heads", type=int, default=32)
+    p.add_argument("--head-dim", type=int, default=128,
+                   help="head_dim of every config (64, 128 or 256)")
     p.add_argument("--kv-heads", type=int, default=None,
                    help="K/V heads (default: equal to --heads)")
     p.add_argument("--seq", type=int, default=65536,
@@ -377,7 +379,7 @@ def main():
     rank = dist.get_rank()
 
     rows = []
-    n, d = args.heads, 128
+    n, d = args.heads, args.head_dim
     if args.window:
         if world != 1:
             p.error("--window is a one-GPU measurement")

@@ -15,7 +15,19 @@ BUILD = os.path.join(PKG_DIR, "csrc", "_build")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-DEVICE_SOURCES = ["attn_fwd.hip", "attn_bwd.hip", "probes.hip"]
+DEVICE_SOURCES = ["attn_fwd.hip", "attn_bwd.hip", "probes.hip",
+                  "attn_d256_fwd.hip", "attn_d256_bwd.hip"]
+# Per-source compiler flags.  The head_dim 256 kernels are built without
+# packed fp32 VALU ops (v_pk_mul_f32 and kin): the accumulator rescale is
+# the one place the compiler would form them, and scalar fp32 ops keep the
+# result independent of their operand forms.  The older sources keep the
+# flags their tuned code was measured with.
+EXTRA_FLAGS = {
+    "attn_d256_fwd.hip": ["-Xclang", "-target-feature", "-Xclang",
+                          "-packed-fp32-ops"],
+    "attn_d256_bwd.hip": ["-Xclang", "-target-feature", "-Xclang",
+                          "-packed-fp32-ops"],
+}
 HOST_SOURCES = ["ext_torch.cpp"]
 
 
@@ -57,7 +69,8 @@ def build(verbose=True, force=False):
         op = os.path.join(BUILD, src.replace(".hip", ".o"))
         objs.append(op)
         if force or _newer(sp, op) or any(_newer(h, op) for h in hdrs):
-            _run([HIPCC, *common, "-c", sp, "-o", op], verbose)
+            _run([HIPCC, *common, *EXTRA_FLAGS.get(src, []), "-c", sp, "-o",
+                  op], verbose)
     for src in HOST_SOURCES:
         sp = os.path.join(CSRC, src)
         op = os.path.join(BUILD, src.replace(".cpp", ".o"))

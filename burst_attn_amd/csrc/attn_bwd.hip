@@ -28,6 +28,7 @@
 // Operand scheme and LDS swizzle: see attn_common.h.
 
 #include "attn_common.h"
+#include "attn_d256.h"
 #include "attn_host.h"
 #include "bwd_plans.h"
 #include "gqa_heads.h"
@@ -1094,7 +1095,7 @@ extern "C" int bahip_attn_bwd_preprocess(
     return ba_fail(BAHIP_ERR_DTYPE_MISMATCH,
                    "o / dout dtype mismatch (%d vs %d)", o_dtype, do_dtype);
   dim3 grid((unsigned)((S + 31) / 32), (unsigned)N, (unsigned)B);
-  return ba_dispatch_td(D, o_dtype, [&](auto td) {
+  const auto go = [&](auto td) {
     using T = typename decltype(td)::type;
     bwd_preprocess_kernel<T, decltype(td)::D>
         <<<grid, 256, 0, (hipStream_t)stream>>>(
@@ -1102,7 +1103,9 @@ extern "C" int bahip_attn_bwd_preprocess(
             o_strides[1], o_strides[2], do_strides[0], do_strides[1],
             do_strides[2]);
     return ba_launch_status();
-  });
+  };
+  return D == BA_D256 ? ba_dispatch_t256(o_dtype, go)
+                      : ba_dispatch_td(D, o_dtype, go);
 }
 
 // ---- backward launch layer --------------------------------------------
@@ -1115,17 +1118,8 @@ extern "C" int bahip_attn_bwd_preprocess(
 // expand a struct into the <<<>>> call and derive the grid, and
 // tools/dkq_probe.hip launches through the same pairs.  bwd_dq_kernel and
 // bwd_dkv_kernel take the same list — the inputs, one fp32 accumulator
-// (dq; dv for MODE 0, dk for MODE 1) and its strides — so they share one.
-struct bwd_dq_args {
-  const void *dout, *q, *k, *v;
-  const float *delta, *lse;
-  float* out;
-  int Sq, Sk, N, G;
-  int64_t g_sb, g_ss, g_sh, q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss,
-      v_sh, d_sb, d_sh, l_sb, l_sh, o_sb, o_ss, o_sh;
-  float scale;
-  int causal;
-};
+// (dq; dv for MODE 0, dk for MODE 1) and its strides — so they share one
+// (bwd_dq_args, attn_host.h).
 using bwd_dkv_args = bwd_dq_args;
 using bwd_dq_kernel_t = decltype(&bwd_dq_kernel<_Float16, 128, 0>);
 static_assert(
@@ -1290,6 +1284,25 @@ static int bwd_entry(
   };
   const bwd_dq_args dqa = acc_into(dq, dqs);
   const bwd_dkv_args dva = acc_into(dv, dvs), dka = acc_into(dk, dks);
+  if (D == BA_D256) {
+    // head_dim 256: the default plan's three kernels in their one-wave-per-
+    // SIMD form (attn_d256.h), the plain call only
+    if (seg || band)
+      return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                     "head_dim 256 does not support %s (plain calls only)",
+                     seg ? "segment ids" : "a band");
+    const ba_seg_verdict sv = ba_seg_bwd_support(kn);
+    if (sv.knob)
+      return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                     "%s=%d does not support head_dim 256 (default backward "
+                     "plan only)",
+                     sv.knob, sv.value);
+    if (B < 1 || B > 65535 || N > 65535 || Sq < 1 || Sk < 1)
+      return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                     "head_dim 256: unsupported shape B=%d Sq=%d Sk=%d N=%d",
+                     (int)B, (int)Sq, (int)Sk, (int)N);
+    return ba_d256_bwd(dqa, dva, dka, B, dtype, (hipStream_t)stream);
+  }
   if (seg) {
     // the default plan's kernels in their segment form, after the pre-pass
     // of both side pairs, all on `stream`

@@ -25,6 +25,7 @@
 //   * epilogue: o = O^T / l (fp32 out), lse = ln2*(m2 + log2(l)).
 
 #include "attn_common.h"
+#include "attn_d256.h"
 #include "attn_host.h"
 #include "fwd_variants.h"
 #include "gqa_heads.h"
@@ -1057,22 +1058,7 @@ int ba_seg_prepass(const int32_t* own, int64_t own_sb, int64_t S_own,
 extern "C" const char* bahip_last_error(void) { return ba_g_err; }
 
 // ---- forward launch layer ---------------------------------------------
-// One field per attn_fwd_kernel parameter, in kernel order.  launch_fwd
-// expands it into the <<<>>> call; the module-launched path hands it to
-// the runtime as the packed kernarg buffer (explicit arguments only: the
-// HIP runtime appends the hidden ones itself — verified by tools/asm_probe).
-struct fwd_args {
-  const void *q, *k, *v;
-  float *o, *lse;
-  int Sq, Sk, N, G;
-  int64_t q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh;
-  float scale;
-  int causal;
-  float *st_acc, *st_m, *st_l;
-  int64_t a_sb, a_ss, a_sh, ml_sb, ml_sh;
-  int carry_in;
-};
-
+// fwd_args (attn_host.h) mirrors attn_fwd_kernel's parameter list.
 using production_kernel_t = decltype(&attn_fwd_kernel<
     _Float16, 128, 64, 1, BA_FWD_PRODUCTION.vpath, BA_FWD_PRODUCTION.subt,
     BA_FWD_PRODUCTION.nt, BA_FWD_PRODUCTION.nbuf, BA_FWD_PRODUCTION.kreg>);
@@ -1330,6 +1316,24 @@ static int fwd_entry(void* hip_function, int out_state, const void* q,
                       qs[0], qs[1], qs[2], ks[0], ks[1], ks[2],
                       vs[0], vs[1], vs[2], scale, causal, acc, m, l,
                       as[0], as[1], as[2], mls[0], mls[1], carry_in};
+  if (D == BA_D256) {
+    // head_dim 256: one kernel set of its own (attn_d256.h), the plain call
+    // only; the V^T workspace is ignored and BA_FWD_VT is not consulted
+    const char* what = seg            ? "segment ids"
+                       : band         ? "a band"
+                       : hip_function ? "a module-launched forward"
+                                      : nullptr;
+    if (what)
+      return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                     "head_dim 256 does not support %s (plain calls only)",
+                     what);
+    if (int rc = fwd_default_variant_only("head_dim 256")) return rc;
+    if (B < 1 || B > 65535 || N > 65535 || Sq < 1 || Sk < 1)
+      return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                     "head_dim 256: unsupported shape B=%d Sq=%d Sk=%d N=%d",
+                     (int)B, (int)Sq, (int)Sk, (int)N);
+    return ba_d256_fwd(a, out_state, B, dtype, (hipStream_t)stream);
+  }
   if (seg)
     return fwd_seg_entry(a, *seg, out_state, B, Sq, Sk, D, dtype,
                          (hipStream_t)stream);
@@ -1501,7 +1505,8 @@ extern "C" int bahip_attn_fwd_accum_band(
 extern "C" int bahip_attn_fwd_state_init(
     float* acc, float* m, float* l, int64_t B, int64_t S, int64_t N, int64_t D,
     const int64_t acc_strides[3], const int64_t ml_strides[2], void* stream) {
-  if (B < 1 || B > 65535 || S < 1 || N < 1 || (D != 64 && D != 128))
+  if (B < 1 || B > 65535 || S < 1 || N < 1 ||
+      (D != 64 && D != 128 && D != BA_D256))
     return ba_fail(BAHIP_ERR_UNSUPPORTED,
                    "state init: unsupported shape B=%d S=%d N=%d D=%d", (int)B,
                    (int)S, (int)N, (int)D);
@@ -1567,6 +1572,8 @@ extern "C" int64_t bahip_attn_fwd_workspace_bytes(int64_t B, int64_t Sq,
   ba_fwd_choice c;
   bool use_vt;
   const int64_t G = ba_gqa_group(N, Nk);
+  // head_dim 256 transposes V in the kernel: no image, no workspace
+  if (D == BA_D256) return 0;
   // a bad knob or head pair is reported by the forward call itself
   if (!G || fwd_read_knobs(Sq, G, &c, &use_vt) || !use_vt) return 0;
   return ba_vt_bytes(B, Nk, Sk, D);
@@ -1637,14 +1644,17 @@ extern "C" int bahip_attn_fwd_finalize(const float* acc, const float* m,
                                        const float* l, void* o, float* lse,
                                        int64_t B, int64_t S, int64_t N,
                                        int64_t D, int dtype, void* stream) {
-  const int rows_per_block = (D == 64) ? 64 : 32;  // 4 waves x 64/(D/16)
+  // 4 waves x 64 / (D / 16) rows: 64, 32, 16 for D = 64, 128, 256
+  const int rows_per_block = (D == 64) ? 64 : (D == BA_D256) ? 16 : 32;
   dim3 grid((unsigned)((S + rows_per_block - 1) / rows_per_block), (unsigned)N,
             (unsigned)B);
-  return ba_dispatch_td(D, dtype, [&](auto td) {
+  const auto go = [&](auto td) {
     using T = typename decltype(td)::type;
     attn_fwd_finalize_kernel<T, decltype(td)::D>
         <<<grid, 256, 0, (hipStream_t)stream>>>(acc, m, l, (T*)o, lse, (int)S,
                                                 (int)N);
     return ba_launch_status();
-  });
+  };
+  return D == BA_D256 ? ba_dispatch_t256(dtype, go)
+                      : ba_dispatch_td(D, dtype, go);
 }

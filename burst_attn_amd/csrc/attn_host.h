@@ -69,6 +69,39 @@ struct kernarg_size<void (*)(P...)> {
   }();
 };
 
+// ---- launch argument lists shared by the kernel files ---------------------
+// One field per attn_fwd_kernel parameter, in kernel order.  launch_fwd
+// expands it into the <<<>>> call; the module-launched path hands it to
+// the runtime as the packed kernarg buffer (explicit arguments only: the
+// HIP runtime appends the hidden ones itself — verified by tools/asm_probe).
+// The head_dim 256 forward (attn_d256_fwd.hip) takes the same list.
+struct fwd_args {
+  const void *q, *k, *v;
+  float *o, *lse;
+  int Sq, Sk, N, G;
+  int64_t q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh;
+  float scale;
+  int causal;
+  float *st_acc, *st_m, *st_l;
+  int64_t a_sb, a_ss, a_sh, ml_sb, ml_sh;
+  int carry_in;
+};
+
+// One field per parameter of bwd_dq_kernel and bwd_dkv_kernel (they take the
+// same list: the inputs, one fp32 accumulator — dq; dv for MODE 0, dk for
+// MODE 1 — and its strides), in kernel order.  The head_dim 256 backward
+// kernels (attn_d256_bwd.hip) take it too.
+struct bwd_dq_args {
+  const void *dout, *q, *k, *v;
+  const float *delta, *lse;
+  float* out;
+  int Sq, Sk, N, G;
+  int64_t g_sb, g_ss, g_sh, q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss,
+      v_sh, d_sb, d_sh, l_sb, l_sh, o_sb, o_ss, o_sh;
+  float scale;
+  int causal;
+};
+
 // f(ba_td<T, D>{}) for the supported (head_dim, dtype) pairs, else 1002.
 template <typename T, int D_>
 struct ba_td {
@@ -83,4 +116,16 @@ int ba_dispatch_td(int64_t D, int dtype, F&& f) {
   if (D == 64 && dtype == BAHIP_F16) return f(ba_td<_Float16, 64>{});
   return ba_fail(BAHIP_ERR_UNSUPPORTED, "unsupported head_dim %d / dtype %d",
                  (int)D, dtype);
+}
+
+// head_dim 256 has a kernel set of its own (attn_d256.h), so it is no row of
+// the table above: that table instantiates the D = 64/128 tile kernels, which
+// do not fit 256-wide heads.  The small kernels that do (finalize, delta
+// preprocess) dispatch here when D == 256.
+template <typename F>
+int ba_dispatch_t256(int dtype, F&& f) {
+  if (dtype == BAHIP_BF16) return f(ba_td<__bf16, 256>{});
+  if (dtype == BAHIP_F16) return f(ba_td<_Float16, 256>{});
+  return ba_fail(BAHIP_ERR_UNSUPPORTED, "unsupported head_dim 256 / dtype %d",
+                 dtype);
 }

@@ -312,6 +312,21 @@ def _check_window(window_size, causal, segment_ids):
     return (left, right)
 
 
+def _check_masks_for_head_dim(q, segment_ids, window):
+    """256-wide heads run the plain tile kernels only: refuse the masked
+    forms here, before any round, not as a kernel error in mid-ring."""
+    if q.shape[3] != 256:
+        return
+    missing = ("segment_ids" if segment_ids is not None
+               else "window_size" if window is not None else None)
+    if missing:
+        raise ValueError(
+            f"head_dim 256 with {missing} is not supported yet: the "
+            "segment-id and sliding-window tile kernels exist for head_dim "
+            "64 and 128 only"
+        )
+
+
 def burst_attn_func(
     q: torch.Tensor,
     k: torch.Tensor,
@@ -329,6 +344,7 @@ def burst_attn_func(
 ):
     _check_heads(q, k, v)
     window = _check_window(window_size, causal, segment_ids)
+    _check_masks_for_head_dim(q, segment_ids, window)
     return OpBurstAttn.apply(
         q, k, v, softmax_scale, flash, causal, optimize_bwd_comm,
         deterministic, process_group, double_group,
@@ -354,6 +370,7 @@ def burst_attn_func_striped(
 ):
     _check_heads(q, k, v)
     window = _check_window(window_size, causal, segment_ids)
+    _check_masks_for_head_dim(q, segment_ids, window)
     return OpBurstAttnStrip.apply(
         q, k, v, softmax_scale, flash, causal, optimize_bwd_comm,
         deterministic, process_group, double_group,

@@ -88,6 +88,24 @@
  *     the knob, V is transposed in the kernel, and a module kernel
  *     (hip_function) is never used.  A band together with segment ids has no
  *     entry point.
+ *   - head_dim: D = 64 and 128 run the 8-wave kernels (256 rows per
+ *     workgroup).  D = 256 runs a kernel set of its own, 4 waves per
+ *     workgroup at one wave per SIMD, 128 rows per workgroup (forward and dq:
+ *     grid ceil(Sq/128) x N x B; dK/dV: ceil(Sk/128) x Nk x B), through the
+ *     same entry points: bahip_attn_fwd[_gqa][_ws], bahip_attn_fwd_accum[_gqa]
+ *     [_ws], bahip_attn_fwd_finalize, bahip_attn_fwd_state_init,
+ *     bahip_attn_bwd_preprocess and bahip_attn_bwd[_gqa], fp16 and bf16,
+ *     causal and rectangular tiles, strided slices, GQA, the same state
+ *     contract and the same bitwise-deterministic backward.  At D = 256 the
+ *     forward transposes V in the kernel: a V^T workspace argument is
+ *     ignored, bahip_attn_fwd_workspace_bytes returns 0 and BA_FWD_VT is not
+ *     consulted.  Not available at D = 256, each returning
+ *     BAHIP_ERR_UNSUPPORTED with a message that names what was asked, nothing
+ *     launched: the *_seg entry points with ids and the *_band entry points;
+ *     a non-null hip_function; a BA_FWD_* selection other than the default
+ *     variant; BA_BWD_FUSED=1/2, BA_BWD_DK_FLIP=1, BA_DQ_PIPE=1.  A knob value
+ *     outside its set is BAHIP_ERR_BAD_KNOB as everywhere.  Any other D
+ *     (96 included) returns BAHIP_ERR_UNSUPPORTED.
  *   - stream is a hipStream_t.
  * Returns 0 on success; nonzero = error.  Every nonzero return sets the
  * calling thread's bahip_last_error() message and every success clears it.
@@ -105,7 +123,8 @@ extern "C" {
 #define BAHIP_BF16 1
 
 #define BAHIP_ERR_CAUSAL_SHAPE 1001   /* causal with Sq != Sk */
-#define BAHIP_ERR_UNSUPPORTED 1002    /* head_dim not 64/128, dtype, or
+#define BAHIP_ERR_UNSUPPORTED 1002    /* head_dim not 64/128/256, dtype, a
+                                         form D = 256 does not have, or
                                          an invalid (N, Nk) head pair */
 #define BAHIP_ERR_DTYPE_MISMATCH 1003 /* o / dout dtypes differ */
 #define BAHIP_ERR_BAD_KNOB 1004       /* a BA_FWD_* knob, BA_BWD_FUSED,

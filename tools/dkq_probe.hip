@@ -4,7 +4,8 @@
 // pinpoints which component (K^T reads, ds_add reduce, global atomics,
 // LDS size, barriers) carries a slowdown.
 //
-// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/dkq_probe.hip -o tools/dkq_probe
+// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/dkq_probe.hip \
+//        burst_attn_amd/csrc/attn_d256_bwd.hip -o tools/dkq_probe
 #include "../burst_attn_amd/csrc/attn_bwd.hip"
 
 #include <stdio.h>
