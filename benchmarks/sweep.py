@@ -33,10 +33,17 @@ its ratio to the dense causal row and the ideal ratio: the (256-row block,
 under the causal triangle, counted with the arithmetic of
 csrc/band_support.h.  TFLOPS of the window rows count the visible pairs only.
 
+Logit soft-capping:
+  python benchmarks/sweep.py --softcap 30
+runs, at --seq (65536), dense causal and then the same call with
+softcap=30, and reports next to each capped time its ratio to the plain row
+of the same run.  The FLOPs model is the plain one (the tanh is not counted).
+
 Row fields mirror the reference's results_torch.jsonl semantics.
 """
 
 import argparse
+import functools
 import json
 import math
 import os
@@ -74,7 +81,7 @@ def timeit(fn, steps, warmup):
 
 
 def bench_burst(args, b, s_global, n, d, causal, striped, opt_bwd, steps, warmup,
-                nk=None):
+                nk=None, softcap=0.0):
     from burst_attn_amd import burst_attn_func, burst_attn_func_striped
 
     world = dist.get_world_size()
@@ -86,6 +93,8 @@ def bench_burst(args, b, s_global, n, d, causal, striped, opt_bwd, steps, warmup
     mk = lambda h=n: torch.randn(b, s_local, h, d, generator=g).to(dtype).cuda()
     q, k, v, do = mk(), mk(nk), mk(nk), mk()
     func = burst_attn_func_striped if striped else burst_attn_func
+    if softcap:
+        func = functools.partial(func, softcap=softcap)
 
     def fwd():
         with torch.no_grad():
@@ -103,7 +112,7 @@ def bench_burst(args, b, s_global, n, d, causal, striped, opt_bwd, steps, warmup
         "method": "burst_striped" if striped else "burst",
         "b": b, "s": s_global, "n": n, "nk": nk, "d": d,
         "causal": causal, "opt_bwd": opt_bwd, "wsize": world,
-        "dtype": args.dtype,
+        "dtype": args.dtype, **({"softcap": softcap} if softcap else {}),
         "fwd_ms": round(t_f * 1e3, 2),
         "fwd_tflops_per_gpu": round(f / t_f / 1e12 / world, 2),
         "fwdbwd_ms": round(t_fb * 1e3, 2),
@@ -363,6 +372,9 @@ def main():
                    help="run dense causal at --seq and causal with "
                         "window_size=(L, R) (R defaults to 0); repeatable; "
                         "replaces --configs")
+    p.add_argument("--softcap", type=float, action="append", default=None,
+                   help="run dense causal at --seq and the same call with "
+                        "this softcap; repeatable; replaces --configs")
     args = p.parse_args()
     nk = args.heads if args.kv_heads is None else args.kv_heads
     if nk < 1 or args.heads % nk:
@@ -395,6 +407,19 @@ def main():
         for w in windows:
             rows.append(bench_window(args, args.seq, n, nk, d, w, dense,
                                      args.steps, args.warmup))
+    elif args.softcap:
+        if world != 1:
+            p.error("--softcap is a one-GPU measurement")
+        plain = bench_burst(args, 1, args.seq, n, d, True, False, False,
+                            args.steps, args.warmup, nk)
+        rows.append(plain)
+        for cap in args.softcap:
+            r = bench_burst(args, 1, args.seq, n, d, True, False, False,
+                            args.steps, args.warmup, nk, softcap=cap)
+            r["fwd_ratio_to_plain"] = round(r["fwd_ms"] / plain["fwd_ms"], 4)
+            r["fwdbwd_ratio_to_plain"] = round(
+                r["fwdbwd_ms"] / plain["fwdbwd_ms"], 4)
+            rows.append(r)
     elif args.configs == "quick":  # 1-GPU-friendly sweep
         for s in (16384, 32768, 65536):
             for causal in (False, True):

@@ -74,7 +74,11 @@ constexpr int KVBLK = 64;
 // SEG: empty = the plain kernel; one ba_seg_args = the segment-id form
 // (attn_common.h; the forward's rules: id equality in `valid`, the block's
 // kv tile range from the pre-pass, per-wave tile skip by (min, max), an
-// empty range leaves before the first barrier having added nothing).
+// empty range leaves before the first barrier having added nothing).  One
+// ba_band_args = the band form.  One ba_cap_args = the soft-capped form
+// (attn_common.h): t = tanh(.) recomputed from the raw score,
+// p = exp2(t * c2cap - lse2), dS = p * (dP - delta) * (1 - t^2) * scale; the
+// mask stays on the exponent, where the plain kernel has it.
 template <typename T, int D, int DQP = 0, typename... SEG>
 __global__ __launch_bounds__(512) void bwd_dq_kernel(
     const T* __restrict__ dout, const T* __restrict__ q,
@@ -91,10 +95,13 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
   using MT = mfma_traits<T>;
   using frag = typename MT::frag;
   constexpr bool HAS_BAND = ba_pack_is<ba_band_args, SEG...>;
-  constexpr bool HAS_SEG = sizeof...(SEG) != 0 && !HAS_BAND;
+  constexpr bool HAS_CAP = ba_pack_is<ba_cap_args, SEG...>;
+  constexpr bool HAS_SEG = sizeof...(SEG) != 0 && !HAS_BAND && !HAS_CAP;
   constexpr bool HAS_MASK = HAS_SEG || HAS_BAND;
-  static_assert(!HAS_MASK || (sizeof...(SEG) == 1 && DQP == 0),
-                "segment ids / band: the default dq kernel");
+  static_assert(!(HAS_MASK || HAS_CAP) || (sizeof...(SEG) == 1 && DQP == 0),
+                "segment ids / band / softcap: the default dq kernel");
+  ba_cap_args cp = {0.f, 0.f};
+  if constexpr (HAS_CAP) cp = ba_cap_of(seg...);
   // band form: the band is the whole mask (the launcher folded causal in)
   if constexpr (HAS_BAND) causal = 0;
   constexpr int SWZ = (D == 128) ? 15 : 7;   // row-major images (2*D B rows)
@@ -299,9 +306,17 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
             valid = valid && (!seg_mask || kseg[min(kv_g, Sk - 1)] == qid);
           if constexpr (HAS_BAND)
             valid = valid && ba_band_visible(q_row, kv_g, bd);
+          if constexpr (HAS_CAP) {
+            const float t = ba_cap_tanh(st[r], cp.a);
+            const float e =
+                valid ? __builtin_fmaf(t, cp.c2, -lse2) : BA_NEG_BIG;
+            st[r] = ba_exp2(e) * (dpt[r] - dlt) * __builtin_fmaf(-t, t, 1.f) *
+                    scale;
+          } else {
           const float e = valid ? __builtin_fmaf(st[r], c2, -lse2) : BA_NEG_BIG;
           const float p = ba_exp2(e);
           st[r] = p * (dpt[r] - dlt) * scale;
+          }
         }
         frag dsf[2];
         ba_build_frag_pair<T>(st, dsf);
@@ -358,7 +373,12 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
 // (attn_common.h), the dq kernel's with the sides swapped: the lane's kv id
 // against the q ids of a tile, the block's q tile range from the pre-pass
 // (the same for every member of a group, so the flattened stream and its
-// "next head's first tile" prefetch only see another t0 and nt).
+// "next head's first tile" prefetch only see another t0 and nt).  One
+// ba_band_args = the band form.  One ba_cap_args = the soft-capped form: the
+// tanh needs the raw score, so -lse*log2e/c2cap leaves the S accumulator for
+// one of its own (the same one-MFMA broadcast of the row constant, 16 more
+// registers), and p = exp2((t + that) * c2cap), dS = p * dP' * (1 - t^2) *
+// scale with dP' = dP - delta from the fold as before.
 template <typename T, int D, int MODE, int QBLK = 64, int GQA = 0,
           typename... SEG>
 __global__ __launch_bounds__(512) void bwd_dkv_kernel(
@@ -376,8 +396,12 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
   using MT = mfma_traits<T>;
   using frag = typename MT::frag;
   constexpr bool HAS_BAND = ba_pack_is<ba_band_args, SEG...>;
-  constexpr bool HAS_SEG = sizeof...(SEG) != 0 && !HAS_BAND;
+  constexpr bool HAS_CAP = ba_pack_is<ba_cap_args, SEG...>;
+  constexpr bool HAS_SEG = sizeof...(SEG) != 0 && !HAS_BAND && !HAS_CAP;
   constexpr bool HAS_MASK = HAS_SEG || HAS_BAND;
+  static_assert(!HAS_CAP || QBLK == 64, "softcap: the default q tile");
+  ba_cap_args cp = {0.f, 0.f};
+  if constexpr (HAS_CAP) cp = ba_cap_of(seg...);
   static_assert(!HAS_MASK || (sizeof...(SEG) == 1 && QBLK == BA_SEG_TILE &&
                               QBLK == BA_BAND_TILE),
                 "segment ids / band: q tiles of the pre-pass's tile size");
@@ -589,7 +613,8 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
           a_lse = __builtin_bit_cast(frag, z);
           a_dlt = __builtin_bit_cast(frag, z);
           if (hi == 0) {
-            const float av = -ld2.x / c2;
+            // cap form: the row constant in units of t (see lt below)
+            const float av = -ld2.x / (HAS_CAP ? cp.c2 : c2);
             const T ah = (T)av;
             a_lse[0] = ah;
             a_lse[1] = (T)(av - (float)ah);
@@ -601,7 +626,9 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
           }
           ones0 = ones01;
         }
-        f32x16_t st = MT::mma(a_lse, ones01, (f32x16_t)(0.f));
+        // cap form: lt = -lse2 / c2cap per row, beside raw scores in st
+        f32x16_t lt = MT::mma(a_lse, ones01, (f32x16_t)(0.f));
+        f32x16_t st = HAS_CAP ? (f32x16_t)(0.f) : lt;
         f32x16_t dpt = (f32x16_t)(0.f);
         if (MODE == 1) dpt = MT::mma(a_dlt, ones0, dpt);
 #pragma unroll
@@ -625,10 +652,18 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
             valid = valid && (!seg_mask || qseg[min(q_g, Sq - 1)] == kid);
           if constexpr (HAS_BAND)
             valid = valid && ba_band_visible(kv_col, q_g, bd);
+          if constexpr (HAS_CAP) {
+            const float t = ba_cap_tanh(st[r], cp.a);
+            const float p = ba_exp2(valid ? (t + lt[r]) * cp.c2 : BA_NEG_BIG);
+            st[r] = (MODE == 0) ? p
+                                : p * dpt[r] * __builtin_fmaf(-t, t, 1.f) *
+                                      scale;
+          } else {
           const float e = valid ? st[r] * c2 : BA_NEG_BIG;
           const float p = ba_exp2(e);
           // MODE_DV: P; MODE_DK: dS
           st[r] = (MODE == 0) ? p : p * dpt[r] * scale;
+          }
         }
         frag f01[2];
         ba_build_frag_pair<T>(st, f01);
@@ -1086,6 +1121,9 @@ __global__ __launch_bounds__(512) void bwd_dkq_kernel(
 
 }  // namespace
 
+// attn_bwd_softcap.hip includes this file for the kernel templates alone
+#ifndef BA_KERNELS_ONLY
+
 // ====================== launchers =====================================
 extern "C" int bahip_attn_bwd_preprocess(
     const void* o, const void* dout, float* delta, int64_t B, int64_t S,
@@ -1238,8 +1276,8 @@ struct bwd_band_call {
   int64_t lo, hi;
 };
 
-// Shared body of the backward entry points; seg and band null = the plain
-// call.
+// Shared body of the backward entry points; seg and band null and softcap 0
+// = the plain call.
 static int bwd_entry(
     const void* dout, const void* q, const void* k, const void* v,
     const float* delta, const float* lse, float* dq, float* dk, float* dv,
@@ -1248,7 +1286,8 @@ static int bwd_entry(
     const int64_t vs[3], const int64_t ds[2], const int64_t ls[2],
     const int64_t dqs[3], const int64_t dks[3], const int64_t dvs[3],
     float scale, int causal, int deterministic, int dtype, void* stream,
-    const bwd_seg_call* seg, const bwd_band_call* band = nullptr) {
+    const bwd_seg_call* seg, const bwd_band_call* band = nullptr,
+    float softcap = 0.f) {
   (void)deterministic;  // only atomic6 is not deterministic by construction
   if (causal && Sq != Sk)
     return ba_fail(BAHIP_ERR_CAUSAL_SHAPE,
@@ -1270,6 +1309,15 @@ static int bwd_entry(
   if (plan.verdict == BA_BWD_BAD_VALUE)
     return ba_fail(BAHIP_ERR_BAD_KNOB, "%s=%d is not an accepted value",
                    plan.knob, plan.value);
+  if (softcap > 0.f) {
+    // the soft-capped kernels exist for the default plan only, at every D
+    const ba_seg_verdict sv = ba_seg_bwd_support(kn);
+    if (sv.knob)
+      return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                     "%s=%d does not support softcap (default backward plan "
+                     "only)",
+                     sv.knob, sv.value);
+  }
   if (plan.verdict == BA_BWD_NO_GQA)
     return ba_fail(BAHIP_ERR_UNSUPPORTED,
                    "%s=%d does not support grouped-query heads "
@@ -1301,6 +1349,9 @@ static int bwd_entry(
       return ba_fail(BAHIP_ERR_UNSUPPORTED,
                      "head_dim 256: unsupported shape B=%d Sq=%d Sk=%d N=%d",
                      (int)B, (int)Sq, (int)Sk, (int)N);
+    if (softcap > 0.f)
+      return ba_d256_bwd_cap(dqa, dva, dka, ba_cap_for(scale, softcap), B,
+                             dtype, (hipStream_t)stream);
     return ba_d256_bwd(dqa, dva, dka, B, dtype, (hipStream_t)stream);
   }
   if (seg) {
@@ -1377,6 +1428,16 @@ static int bwd_entry(
       launch_dkv_band<T, TD, 1>(dka, bd, B, st);
       return ba_launch_status();
     });
+  }
+  if (softcap > 0.f) {
+    // the default plan's kernels in their soft-capped form
+    // (attn_bwd_softcap.hip); the knobs were checked above
+    if (B < 1 || B > 65535 || Sq < 1 || Sk < 1)
+      return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                     "softcap: unsupported shape B=%d Sq=%d Sk=%d", (int)B,
+                     (int)Sq, (int)Sk);
+    return ba_cap_bwd(dqa, dva, dka, ba_cap_for(scale, softcap), B, D, dtype,
+                      (hipStream_t)stream);
   }
   const bwd_dkq_args dkqa = {
       dout, q, k, v, delta, lse, dq, dk, dv, iSq, iSk, iN,
@@ -1457,6 +1518,24 @@ extern "C" int bahip_attn_bwd_band(
                    deterministic, dtype, stream, nullptr, &bc);
 }
 
+extern "C" int bahip_attn_bwd_softcap(
+    const void* dout, const void* q, const void* k, const void* v,
+    const float* delta, const float* lse, float* dq, float* dk, float* dv,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t gs[3], const int64_t qs[3], const int64_t ks[3],
+    const int64_t vs[3], const int64_t ds[2], const int64_t ls[2],
+    const int64_t dqs[3], const int64_t dks[3], const int64_t dvs[3],
+    float scale, int causal, int deterministic, int dtype, float softcap,
+    void* stream) {
+  if (!ba_cap_valid(softcap))
+    return ba_fail(BAHIP_ERR_SOFTCAP,
+                   "softcap=%g must be 0 (off) or a positive finite number",
+                   (double)softcap);
+  return bwd_entry(dout, q, k, v, delta, lse, dq, dk, dv, B, Sq, Sk, N, Nk, D,
+                   gs, qs, ks, vs, ds, ls, dqs, dks, dvs, scale, causal,
+                   deterministic, dtype, stream, nullptr, nullptr, softcap);
+}
+
 // the equal-heads symbol: Nk = N
 extern "C" int bahip_attn_bwd(
     const void* dout, const void* q, const void* k, const void* v,
@@ -1474,3 +1553,5 @@ extern "C" int bahip_attn_bwd(
                             dk_strides, dv_strides, softmax_scale, causal,
                             deterministic, dtype, stream);
 }
+
+#endif  // BA_KERNELS_ONLY

@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "band_support.h"
+#include "cap_support.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
@@ -170,6 +171,25 @@ template <typename A, typename... P>
 constexpr bool ba_pack_is = sizeof...(P) == 1 && (ba_same_t<A, P>::value && ...);
 __device__ __forceinline__ ba_band_args ba_band_of(const ba_band_args& b) {
   return b;
+}
+
+// ---- logit soft-capping -------------------------------------------------
+// The cap form of a kernel takes one ba_cap_args in the same trailing pack:
+// every score s = q.k becomes softcap * tanh(s * scale / softcap) before the
+// softmax, and nothing masks but the kernel's own range and causal rule.  The
+// launcher precomputes its two constants (cap_support.h): exp2(s * a) is
+// e^(2x) of the tanh's argument x, and c2 = softcap * log2(e) takes
+// scale * log2(e)'s place in the exp2-domain softmax.
+__device__ __forceinline__ ba_cap_args ba_cap_of(const ba_cap_args& c) {
+  return c;
+}
+// t = tanh(x) = 1 - 2 / (1 + e^(2x)) of a raw score: one v_exp_f32, one
+// v_rcp_f32, no branch.  Both ends saturate by themselves (exp2 -> inf gives
+// rcp = 0 and t = 1, exp2 -> 0 gives t = -1); near x = 0 the subtraction
+// leaves an absolute error of a few 1e-7, which c2 (43 at softcap 30) scales
+// to far below the 16-bit rounding of P.
+__device__ __forceinline__ float ba_cap_tanh(float s, float a) {
+  return __builtin_fmaf(-2.f, __builtin_amdgcn_rcpf(1.f + ba_exp2(s * a)), 1.f);
 }
 
 // min and max of x over the wave, as wave-uniform (scalar) values

@@ -23,7 +23,8 @@
 // (unnormalised acc, m in the exp2 domain, l) with BA_NEG_BIG as the empty
 // level), so finalize, state init and the ring's merge serve both sets.
 // No segment-id, band, module or experiment-variant form exists here: the
-// entry points refuse those at D = 256 (attn_fwd.hip / attn_bwd.hip).
+// entry points refuse those at D = 256 (attn_fwd.hip / attn_bwd.hip).  The
+// soft-capped form does: each kernel takes one ba_cap_args in a trailing pack.
 #pragma once
 #include "attn_common.h"
 #include "attn_host.h"
@@ -67,3 +68,9 @@ int ba_d256_fwd(const fwd_args& a, int out_state, int64_t B, int dtype,
 int ba_d256_bwd(const bwd_dq_args& dq, const bwd_dq_args& dv,
                 const bwd_dq_args& dk, int64_t B, int dtype,
                 hipStream_t stream);
+// the same in the soft-capped form (attn_common.h, cap_support.h)
+int ba_d256_fwd_cap(const fwd_args& a, const ba_cap_args& cp, int out_state,
+                    int64_t B, int dtype, hipStream_t stream);
+int ba_d256_bwd_cap(const bwd_dq_args& dq, const bwd_dq_args& dv,
+                    const bwd_dq_args& dk, const ba_cap_args& cp, int64_t B,
+                    int dtype, hipStream_t stream);

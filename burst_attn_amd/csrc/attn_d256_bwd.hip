@@ -9,6 +9,10 @@
 //     ds = p * (dp - delta) * scale;   dq += ds k;    dk += ds^T q
 // Streamed tiles are 32 rows (one MFMA subtile); their transposed images
 // have 64-byte rows (ba_swz64, attn_d256.h).
+// CAP: empty = the plain kernels.  One ba_cap_args = the soft-capped form
+// (attn_common.h): t = tanh(.) recomputed from the raw score,
+//     p = exp2(t * c2cap - lse * log2e);  ds = p * (dp - delta) * (1 - t^2) * scale
+// with the mask applied to the exponent, never to the raw score.
 
 #include "attn_d256.h"
 
@@ -43,7 +47,7 @@ __device__ __forceinline__ int rowmajor_byte(int row, int col8) {
 // tiles of 32 kv rows stream through LDS, double buffered (96 KiB).
 //   S^T = mfma(K, Q); dP^T = mfma(V, dO); dS^T in-lane (lse and delta are
 //   lane-local); dQ^T += mfma(K^T, dS^T)
-template <typename T>
+template <typename T, typename... CAP>
 __global__ __launch_bounds__(NT) void bwd_d256_dq_kernel(
     const T* __restrict__ dout, const T* __restrict__ q,
     const T* __restrict__ k, const T* __restrict__ v,
@@ -55,9 +59,13 @@ __global__ __launch_bounds__(NT) void bwd_d256_dq_kernel(
     int64_t v_sb, int64_t v_ss, int64_t v_sh,
     int64_t d_sb, int64_t d_sh, int64_t l_sb, int64_t l_sh,
     int64_t dq_sb, int64_t dq_ss, int64_t dq_sh,
-    float scale, int causal) {
+    float scale, int causal, CAP... cap) {
   using MT = mfma_traits<T>;
   using frag = typename MT::frag;
+  constexpr bool HAS_CAP = ba_pack_is<ba_cap_args, CAP...>;
+  static_assert(HAS_CAP || sizeof...(CAP) == 0, "the pack: one ba_cap_args");
+  ba_cap_args cp = {0.f, 0.f};
+  if constexpr (HAS_CAP) cp = ba_cap_of(cap...);
 
   // [2 buffers][K row-major | V row-major | K^T transposed]
   __shared__ T lds[2 * 3 * TILE * D];
@@ -157,8 +165,16 @@ __global__ __launch_bounds__(NT) void bwd_d256_dq_kernel(
         const int kv_g = kv0 + ba_crow(r, 0) + 4 * hi;
         const bool valid =
             kv_g < Sk && (!causal || kv_g <= q_row) && q_row < Sq;
-        const float e = valid ? __builtin_fmaf(st[r], c2, -lse2) : BA_NEG_BIG;
-        st[r] = ba_exp2(e) * (dpt[r] - dlt) * scale;
+        if constexpr (HAS_CAP) {
+          const float t = ba_cap_tanh(st[r], cp.a);
+          const float e = valid ? __builtin_fmaf(t, cp.c2, -lse2) : BA_NEG_BIG;
+          st[r] = ba_exp2(e) * (dpt[r] - dlt) * __builtin_fmaf(-t, t, 1.f) *
+                  scale;
+        } else {
+          const float e =
+              valid ? __builtin_fmaf(st[r], c2, -lse2) : BA_NEG_BIG;
+          st[r] = ba_exp2(e) * (dpt[r] - dlt) * scale;
+        }
       }
       frag dsf[2];
       ba_build_frag_pair<T>(st, dsf);
@@ -197,7 +213,7 @@ __global__ __launch_bounds__(NT) void bwd_d256_dq_kernel(
 // row is the MFMA row axis, so lse * log2e and delta are per-register, not
 // per-lane: each tile's 32 + 32 values are staged behind its images and
 // read back as 4-float row groups.
-template <typename T, int MODE>
+template <typename T, int MODE, typename... CAP>
 __global__ __launch_bounds__(NT) void bwd_d256_dkv_kernel(
     const T* __restrict__ dout, const T* __restrict__ q,
     const T* __restrict__ k, const T* __restrict__ v,
@@ -209,9 +225,13 @@ __global__ __launch_bounds__(NT) void bwd_d256_dkv_kernel(
     int64_t v_sb, int64_t v_ss, int64_t v_sh,
     int64_t d_sb, int64_t d_sh, int64_t l_sb, int64_t l_sh,
     int64_t o_sb, int64_t o_ss, int64_t o_sh,
-    float scale, int causal) {
+    float scale, int causal, CAP... cap) {
   using MT = mfma_traits<T>;
   using frag = typename MT::frag;
+  constexpr bool HAS_CAP = ba_pack_is<ba_cap_args, CAP...>;
+  static_assert(HAS_CAP || sizeof...(CAP) == 0, "the pack: one ba_cap_args");
+  ba_cap_args cp = {0.f, 0.f};
+  if constexpr (HAS_CAP) cp = ba_cap_of(cap...);
   // images per buffer: dV: [Q row-major | dO^T]; dK: [Q | dO | Q^T]
   constexpr int IMGS = MODE == 0 ? 2 : 3;
   constexpr int ROWC = 2 * TILE * (int)(sizeof(float) / sizeof(T));
@@ -358,10 +378,20 @@ __global__ __launch_bounds__(NT) void bwd_d256_dkv_kernel(
             const int q_g = q0 + ba_crow(r, 0) + 4 * hi;
             const bool valid =
                 q_g < Sq && kv_col < Sk && (!causal || q_g >= kv_col);
-            const float e =
-                valid ? __builtin_fmaf(st[r], c2, -lv[j]) : BA_NEG_BIG;
-            const float p = ba_exp2(e);
-            st[r] = (MODE == 0) ? p : p * (dpt[r] - dv[j]) * scale;  // P : dS
+            if constexpr (HAS_CAP) {
+              const float t = ba_cap_tanh(st[r], cp.a);
+              const float e =
+                  valid ? __builtin_fmaf(t, cp.c2, -lv[j]) : BA_NEG_BIG;
+              const float p = ba_exp2(e);
+              st[r] = (MODE == 0) ? p
+                                  : p * (dpt[r] - dv[j]) *
+                                        __builtin_fmaf(-t, t, 1.f) * scale;
+            } else {
+              const float e =
+                  valid ? __builtin_fmaf(st[r], c2, -lv[j]) : BA_NEG_BIG;
+              const float p = ba_exp2(e);
+              st[r] = (MODE == 0) ? p : p * (dpt[r] - dv[j]) * scale;  // P : dS
+            }
           }
         }
         frag f01[2];
@@ -392,14 +422,16 @@ __global__ __launch_bounds__(NT) void bwd_d256_dkv_kernel(
   }
 }
 
-template <typename T, typename K>
+// `cap`: nothing, or the ba_cap_args of a soft-capped kernel
+template <typename T, typename K, typename... CAP>
 void launch_d256_acc(K kernel, dim3 grid, const bwd_dq_args& a,
-                     hipStream_t stream) {
+                     hipStream_t stream, CAP... cap) {
   kernel<<<grid, dim3(NT), 0, stream>>>(
       (const T*)a.dout, (const T*)a.q, (const T*)a.k, (const T*)a.v, a.delta,
       a.lse, a.out, a.Sq, a.Sk, a.N, a.G, a.g_sb, a.g_ss, a.g_sh, a.q_sb,
       a.q_ss, a.q_sh, a.k_sb, a.k_ss, a.k_sh, a.v_sb, a.v_ss, a.v_sh, a.d_sb,
-      a.d_sh, a.l_sb, a.l_sh, a.o_sb, a.o_ss, a.o_sh, a.scale, a.causal);
+      a.d_sh, a.l_sb, a.l_sh, a.o_sb, a.o_ss, a.o_sh, a.scale, a.causal,
+      cap...);
 }
 
 }  // namespace
@@ -418,6 +450,27 @@ int ba_d256_bwd(const bwd_dq_args& dq, const bwd_dq_args& dv,
     launch_d256_acc<T>(bwd_d256_dkv_kernel<T, 0>, kgrid, dv, stream);
     BA_CHECK_LAUNCH();
     launch_d256_acc<T>(bwd_d256_dkv_kernel<T, 1>, kgrid, dk, stream);
+    return ba_launch_status();
+  });
+}
+
+int ba_d256_bwd_cap(const bwd_dq_args& dq, const bwd_dq_args& dv,
+                    const bwd_dq_args& dk, const ba_cap_args& cp, int64_t B,
+                    int dtype, hipStream_t stream) {
+  const unsigned qblocks = (unsigned)((dq.Sq + BA_D256_BLOCK - 1) / BA_D256_BLOCK);
+  const unsigned kblocks = (unsigned)((dq.Sk + BA_D256_BLOCK - 1) / BA_D256_BLOCK);
+  const dim3 qgrid(qblocks, (unsigned)dq.N, (unsigned)B);
+  const dim3 kgrid(kblocks, (unsigned)(dq.N / dq.G), (unsigned)B);
+  return ba_dispatch_t256(dtype, [&](auto td) {
+    using T = typename decltype(td)::type;
+    launch_d256_acc<T>(bwd_d256_dq_kernel<T, ba_cap_args>, qgrid, dq, stream,
+                       cp);
+    BA_CHECK_LAUNCH();
+    launch_d256_acc<T>(bwd_d256_dkv_kernel<T, 0, ba_cap_args>, kgrid, dv,
+                       stream, cp);
+    BA_CHECK_LAUNCH();
+    launch_d256_acc<T>(bwd_d256_dkv_kernel<T, 1, ba_cap_args>, kgrid, dk,
+                       stream, cp);
     return ba_launch_status();
   });
 }

@@ -18,12 +18,16 @@
 //     carry-in / carry-out state (acc, m, l), bit-compatible with the
 //     D = 64/128 kernels' so state init, finalize and the ring's merge are
 //     shared.
+//   * CAP: empty = the plain kernel.  One ba_cap_args = the soft-capped form
+//     (attn_common.h), by the rules of attn_fwd.hip's: the row max on raw
+//     scores with only that one value transformed, t = tanh(.) per score,
+//     p = exp2(t * c2cap - m2), and the mask applied to t.
 
 #include "attn_d256.h"
 
 namespace {
 
-template <typename T, int OUT_STATE>
+template <typename T, int OUT_STATE, typename... CAP>
 __global__ __launch_bounds__(BA_D256_NT) void attn_d256_fwd_kernel(
     const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
     float* __restrict__ o, float* __restrict__ lse,
@@ -35,9 +39,11 @@ __global__ __launch_bounds__(BA_D256_NT) void attn_d256_fwd_kernel(
     float* __restrict__ st_acc, float* __restrict__ st_m,
     float* __restrict__ st_l,
     int64_t a_sb, int64_t a_ss, int64_t a_sh,
-    int64_t ml_sb, int64_t ml_sh, int carry_in) {
+    int64_t ml_sb, int64_t ml_sh, int carry_in, CAP... cap) {
   using MT = mfma_traits<T>;
   using frag = typename MT::frag;
+  constexpr bool HAS_CAP = ba_pack_is<ba_cap_args, CAP...>;
+  static_assert(HAS_CAP || sizeof...(CAP) == 0, "the pack: one ba_cap_args");
   constexpr int D = BA_D256;
   constexpr int NT = BA_D256_NT;
   constexpr int KVBLK = 64;
@@ -82,6 +88,8 @@ __global__ __launch_bounds__(BA_D256_NT) void attn_d256_fwd_kernel(
   }
 
   const float c2 = scale * BA_LOG2E;  // exp2-domain scale
+  ba_cap_args cp = {0.f, 0.f};
+  if constexpr (HAS_CAP) cp = ba_cap_of(cap...);
   float m2 = BA_NEG_BIG;
   float lsum = 0.f;
   f32x16_t ot[D / 32];
@@ -180,7 +188,11 @@ __global__ __launch_bounds__(BA_D256_NT) void attn_d256_fwd_kernel(
         {
           float lo, hi2;
           ba_half_pair(tm, lo, hi2);
-          tm = fmaxf(lo, hi2) * c2;
+          // cap form: the capped value of the one max (tanh is increasing)
+          if constexpr (HAS_CAP)
+            tm = ba_cap_tanh(fmaxf(lo, hi2), cp.a) * cp.c2;
+          else
+            tm = fmaxf(lo, hi2) * c2;
         }
         // defer-max: skip the O/l rescale while the running max grows by
         // <= THR; decided before these scores are exponentiated
@@ -195,10 +207,32 @@ __global__ __launch_bounds__(BA_D256_NT) void attn_d256_fwd_kernel(
             for (int r = 0; r < 16; ++r) ot[dt][r] *= alpha;
         }
         float rowsum = 0.f;
+        if constexpr (HAS_CAP) {
+          // m2 is a capped level (>= -c2cap) by now.  A masked entry is
+          // masked on t: tanh of the raw mask level is -1, a finite score
+          // of -softcap that would leak
+          if (!full) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          s[r] = ba_exp2(__builtin_fmaf(s[r], c2, -m2));
-          rowsum += s[r];
+            for (int r = 0; r < 16; ++r) {
+              const float t = ba_cap_tanh(s[r], cp.a);
+              s[r] = ba_exp2(__builtin_fmaf(
+                  s[r] == BA_NEG_BIG ? BA_NEG_BIG : t, cp.c2, -m2));
+              rowsum += s[r];
+            }
+          } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              s[r] =
+                  ba_exp2(__builtin_fmaf(ba_cap_tanh(s[r], cp.a), cp.c2, -m2));
+              rowsum += s[r];
+            }
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            s[r] = ba_exp2(__builtin_fmaf(s[r], c2, -m2));
+            rowsum += s[r];
+          }
         }
         {
           float lo, hi2;
@@ -250,15 +284,18 @@ __global__ __launch_bounds__(BA_D256_NT) void attn_d256_fwd_kernel(
   }
 }
 
-template <typename T, int OUT_STATE>
-void launch_d256_fwd(const fwd_args& a, int64_t B, hipStream_t stream) {
+// `cap`: nothing, or the ba_cap_args of the soft-capped kernel
+template <typename T, int OUT_STATE, typename... CAP>
+void launch_d256_fwd(const fwd_args& a, int64_t B, hipStream_t stream,
+                     CAP... cap) {
   const dim3 grid((unsigned)((a.Sq + BA_D256_BLOCK - 1) / BA_D256_BLOCK),
                   (unsigned)a.N, (unsigned)B);
-  attn_d256_fwd_kernel<T, OUT_STATE><<<grid, dim3(BA_D256_NT), 0, stream>>>(
+  attn_d256_fwd_kernel<T, OUT_STATE, CAP...>
+      <<<grid, dim3(BA_D256_NT), 0, stream>>>(
       (const T*)a.q, (const T*)a.k, (const T*)a.v, a.o, a.lse, a.Sq, a.Sk,
       a.N, a.G, a.q_sb, a.q_ss, a.q_sh, a.k_sb, a.k_ss, a.k_sh, a.v_sb, a.v_ss,
       a.v_sh, a.scale, a.causal, a.st_acc, a.st_m, a.st_l, a.a_sb, a.a_ss,
-      a.a_sh, a.ml_sb, a.ml_sh, a.carry_in);
+      a.a_sh, a.ml_sb, a.ml_sh, a.carry_in, cap...);
 }
 
 }  // namespace
@@ -271,6 +308,18 @@ int ba_d256_fwd(const fwd_args& a, int out_state, int64_t B, int dtype,
       launch_d256_fwd<T, 1>(a, B, stream);
     else
       launch_d256_fwd<T, 0>(a, B, stream);
+    return ba_launch_status();
+  });
+}
+
+int ba_d256_fwd_cap(const fwd_args& a, const ba_cap_args& cp, int out_state,
+                    int64_t B, int dtype, hipStream_t stream) {
+  return ba_dispatch_t256(dtype, [&](auto td) {
+    using T = typename decltype(td)::type;
+    if (out_state)
+      launch_d256_fwd<T, 1>(a, B, stream, cp);
+    else
+      launch_d256_fwd<T, 0>(a, B, stream, cp);
     return ba_launch_status();
   });
 }

@@ -105,7 +105,14 @@ __device__ __forceinline__ int ba_buf_of(ba_dyn d) { return d.value; }
 // tile whose (min, max) ids miss those of its rows; masked entries get
 // weight exactly 0, so a row that sees no key ends with l = 0; a workgroup
 // with an empty range leaves before its first barrier.  Default variant
-// with VSRC=0 only.
+// with VSRC=0 only.  One ba_band_args = the band form.  One ba_cap_args =
+// the soft-capped form (attn_common.h): the row max is taken on raw scores as
+// in the plain kernel (tanh is increasing) and only that one value is
+// transformed before the defer-max test; each score becomes t = tanh(.) and
+// p = exp2(t * c2cap - m2).  A masked entry is masked on t, not on the raw
+// score: tanh of the raw mask level is -1, a finite score of -softcap that
+// would leak.  Same state contract (capped scores are bounded by c2cap, the
+// empty level stays BA_NEG_BIG).  Default variant with VSRC=0 only.
 template <typename T, int D, int KVBLK, int OUT_STATE, int VPATH, int SUBT,
           int NT = 512, int NBUF = 2, int KREG = 0, int VSRC = 0,
           typename... SEG>
@@ -125,10 +132,14 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
   using MT = mfma_traits<T>;
   using frag = typename MT::frag;
   constexpr bool HAS_BAND = ba_pack_is<ba_band_args, SEG...>;
-  constexpr bool HAS_SEG = sizeof...(SEG) != 0 && !HAS_BAND;
+  constexpr bool HAS_CAP = ba_pack_is<ba_cap_args, SEG...>;
+  constexpr bool HAS_SEG = sizeof...(SEG) != 0 && !HAS_BAND && !HAS_CAP;
   // either form: entries can be masked inside the tensors' ranges, so a row
   // may see no key (weight-0 select, l = 0 epilogue)
   constexpr bool HAS_MASK = HAS_SEG || HAS_BAND;
+  static_assert(!HAS_CAP || (VPATH == 0 && SUBT == 1 && NT == 512 &&
+                             NBUF == 2 && KREG == 0 && VSRC == 0),
+                "soft-capping: the default variant, V transposed in-kernel");
   static_assert(!HAS_MASK || (sizeof...(SEG) == 1 && VPATH == 0 && SUBT == 1 &&
                               NT == 512 && NBUF == 2 && KREG == 0 && VSRC == 0),
                 "segment ids / band: the default variant, V transposed "
@@ -288,6 +299,10 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
   }
   const int t_first = HAS_MASK ? trange.x : 0;
   const int nt = HAS_MASK ? trange.y : nt_shape;
+  // cap form: the two constants, and whether the current tile was masked
+  ba_cap_args cp = {0.f, 0.f};
+  bool cap_masked = false;
+  if constexpr (HAS_CAP) cp = ba_cap_of(seg...);
   static_assert(SUBT != 2 || (NBUF == 4 && VPATH == 0),
                 "the T15 pipeline needs NBUF=4 and the V^T image");
   static_assert(SUBT != 3 || (NBUF == 4 && VPATH == 0 && NT == 256),
@@ -355,6 +370,8 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
     } else {
       tm = fmaxf(tm, __shfl_xor(tm, 32));
     }
+    // cap form: the capped value of the one max, in the exp2 domain
+    if constexpr (HAS_CAP) return ba_cap_tanh(tm, cp.a) * cp.c2;
     return tm * c2;
   };
   // online-softmax rescale (lane-local), defer-max (T13): skip the O/l
@@ -388,6 +405,26 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
       for (int r = 0; r < 16; ++r) {
         s[r] = ba_exp2(__builtin_fmaf(s[r], c2, -m2));
         rowsum += s[r];
+      }
+    } else if constexpr (HAS_CAP) {
+      // m2 is a capped level here (>= -c2cap) whatever the tile held: the
+      // rescale above has seen this subtile's transformed max
+      if (cap_masked) {
+        // mask_sub marked the raw scores; the mark moves to t, so that the
+        // exponent is as negative as it is in the plain kernel
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float t = ba_cap_tanh(s[r], cp.a);
+          s[r] = ba_exp2(__builtin_fmaf(s[r] == BA_NEG_BIG ? BA_NEG_BIG : t,
+                                        cp.c2, -m2));
+          rowsum += s[r];
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          s[r] = ba_exp2(__builtin_fmaf(ba_cap_tanh(s[r], cp.a), cp.c2, -m2));
+          rowsum += s[r];
+        }
       }
     } else {
 #pragma unroll
@@ -699,6 +736,7 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
           // per-tile barrier)
           if (KREG == 2) load_next_kfrags(t, kvs, kres);
           if (!full) mask_sub(st, kv0, kvs * 32);
+          if constexpr (HAS_CAP) cap_masked = !full;
           frag pf[2];
           softmax_tail(st, row_max2(st), pf);
 #pragma unroll
@@ -956,6 +994,9 @@ __global__ __launch_bounds__(256) void attn_vt_image_kernel(
   }
 }
 
+// (the pre-pass kernels are no templates: a source that includes this file
+// for the kernel templates alone would emit copies of them)
+#ifndef BA_KERNELS_ONLY
 // ---- segment-id pre-pass (layout: seg_support.h) ------------------------
 // Step 1, one wave per 64-row tile of the streamed side: the tile's
 // (min, max) id, and a per-batch-row flag raised where an id is smaller
@@ -1032,8 +1073,12 @@ __global__ __launch_bounds__(256) void seg_block_range_kernel(
   __syncthreads();
   if (tid == 0) *out = make_int2(s_lo, s_hi);
 }
+#endif  // BA_KERNELS_ONLY
 
 }  // namespace
+
+// attn_fwd_softcap.hip includes this file for the kernel templates alone
+#ifndef BA_KERNELS_ONLY
 
 // ranges of one side pair: `own` is the side whose 256-row blocks the
 // kernel's workgroups hold, `str` the side they stream in 64-row tiles
@@ -1231,6 +1276,33 @@ static int fwd_band_entry(const fwd_args& a, const fwd_band_call& bc,
   });
 }
 
+// ---- soft-capped form ------------------------------------------------------
+// softcap = 0 is the call without it; negative or non-finite is the caller's
+// bug.  *capped says which of the two a valid value is.
+static int ba_softcap_given(float softcap, bool* capped) {
+  if (!ba_cap_valid(softcap))
+    return ba_fail(BAHIP_ERR_SOFTCAP,
+                   "softcap=%g must be 0 (off) or a positive finite number",
+                   (double)softcap);
+  *capped = softcap > 0.f;
+  return 0;
+}
+
+// The forward with a cap: as with ids and bands, the default variant only, V
+// transposed in the kernel (the V^T workspace is ignored), never the module
+// kernel.  The kernels are attn_fwd_softcap.hip's.
+static int fwd_cap_entry(const fwd_args& a, float softcap, int out_state,
+                         int64_t B, int64_t Sq, int64_t Sk, int64_t D,
+                         int dtype, hipStream_t stream) {
+  if (int rc = fwd_default_variant_only("softcap")) return rc;
+  if (B < 1 || B > 65535 || Sq < 1 || Sk < 1)
+    return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                   "softcap: unsupported shape B=%d Sq=%d Sk=%d", (int)B,
+                   (int)Sq, (int)Sk);
+  return ba_cap_fwd(a, ba_cap_for(a.scale, softcap), out_state, B, D, dtype,
+                    stream);
+}
+
 // The per-call knobs: the variant the BA_FWD_* table selects, and whether
 // a call with these shapes stages V from the V^T image (vt_image.h).
 // BA_FWD_VT=1 forces the image wherever the default variant runs, 0 forces
@@ -1299,7 +1371,8 @@ static int fwd_entry(void* hip_function, int out_state, const void* q,
                      float* l, const int64_t* as, const int64_t* mls,
                      int carry_in, void* ws, int64_t ws_bytes, void* stream,
                      const fwd_seg_call* seg = nullptr,
-                     const fwd_band_call* band = nullptr) {
+                     const fwd_band_call* band = nullptr,
+                     float softcap = 0.f) {
   if (causal && Sq != Sk)
     return ba_fail(BAHIP_ERR_CAUSAL_SHAPE,
                    "causal tiles require Sq == Sk (%d vs %d)", (int)Sq,
@@ -1327,11 +1400,16 @@ static int fwd_entry(void* hip_function, int out_state, const void* q,
       return ba_fail(BAHIP_ERR_UNSUPPORTED,
                      "head_dim 256 does not support %s (plain calls only)",
                      what);
-    if (int rc = fwd_default_variant_only("head_dim 256")) return rc;
+    if (int rc = fwd_default_variant_only(
+            softcap > 0.f ? "head_dim 256 with softcap" : "head_dim 256"))
+      return rc;
     if (B < 1 || B > 65535 || N > 65535 || Sq < 1 || Sk < 1)
       return ba_fail(BAHIP_ERR_UNSUPPORTED,
                      "head_dim 256: unsupported shape B=%d Sq=%d Sk=%d N=%d",
                      (int)B, (int)Sq, (int)Sk, (int)N);
+    if (softcap > 0.f)
+      return ba_d256_fwd_cap(a, ba_cap_for(scale, softcap), out_state, B,
+                             dtype, (hipStream_t)stream);
     return ba_d256_fwd(a, out_state, B, dtype, (hipStream_t)stream);
   }
   if (seg)
@@ -1340,6 +1418,9 @@ static int fwd_entry(void* hip_function, int out_state, const void* q,
   if (band)
     return fwd_band_entry(a, *band, out_state, B, Sq, Sk, D, dtype,
                           (hipStream_t)stream);
+  if (softcap > 0.f)
+    return fwd_cap_entry(a, softcap, out_state, B, Sq, Sk, D, dtype,
+                         (hipStream_t)stream);
   if (hip_function) {
     if (D != 128 || (dtype != BAHIP_F16 && dtype != BAHIP_BF16))
       return ba_fail(BAHIP_ERR_UNSUPPORTED,
@@ -1502,6 +1583,38 @@ extern "C" int bahip_attn_fwd_accum_band(
                    nullptr, 0, stream, nullptr, &bc);
 }
 
+extern "C" int bahip_attn_fwd_softcap(
+    const void* q, const void* k, const void* v, float* o, float* lse,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    void* workspace, int64_t workspace_bytes, float softcap, void* stream) {
+  bool capped;
+  if (int rc = ba_softcap_given(softcap, &capped)) return rc;
+  return fwd_entry(nullptr, 0, q, k, v, o, lse, B, Sq, Sk, N, Nk, D, q_strides,
+                   k_strides, v_strides, softmax_scale, causal, dtype, nullptr,
+                   nullptr, nullptr, nullptr, nullptr, 0, workspace,
+                   workspace_bytes, stream, nullptr, nullptr,
+                   capped ? softcap : 0.f);
+}
+
+extern "C" int bahip_attn_fwd_accum_softcap(
+    void* hip_function, const void* q, const void* k, const void* v,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    float* acc, float* m, float* l, const int64_t acc_strides[3],
+    const int64_t ml_strides[2], int carry_in, void* workspace,
+    int64_t workspace_bytes, float softcap, void* stream) {
+  bool capped;
+  if (int rc = ba_softcap_given(softcap, &capped)) return rc;
+  return fwd_entry(hip_function, 1, q, k, v, nullptr, nullptr, B, Sq, Sk, N,
+                   Nk, D, q_strides, k_strides, v_strides, softmax_scale,
+                   causal, dtype, acc, m, l, acc_strides, ml_strides, carry_in,
+                   workspace, workspace_bytes, stream, nullptr, nullptr,
+                   capped ? softcap : 0.f);
+}
+
 extern "C" int bahip_attn_fwd_state_init(
     float* acc, float* m, float* l, int64_t B, int64_t S, int64_t N, int64_t D,
     const int64_t acc_strides[3], const int64_t ml_strides[2], void* stream) {
@@ -1658,3 +1771,5 @@ extern "C" int bahip_attn_fwd_finalize(const float* acc, const float* m,
   return D == BA_D256 ? ba_dispatch_t256(dtype, go)
                       : ba_dispatch_td(D, dtype, go);
 }
+
+#endif  // BA_KERNELS_ONLY

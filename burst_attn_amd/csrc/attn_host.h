@@ -9,6 +9,7 @@
 #include <stdlib.h>
 
 #include "../../include/burst_attn_hip.h"
+#include "cap_support.h"
 
 // One message buffer for both translation units (C++17 inline variable);
 // bahip_last_error() in attn_fwd.hip returns it.
@@ -101,6 +102,17 @@ struct bwd_dq_args {
   float scale;
   int causal;
 };
+
+// Soft-capped form of the D = 64/128 kernels (cap_support.h): the default
+// forward variant and the default backward plan's three kernels, instantiated
+// and launched in attn_fwd_softcap.hip / attn_bwd_softcap.hip, which are built
+// without packed fp32 VALU ops.  The callers have validated shapes, heads and
+// knobs.
+int ba_cap_fwd(const fwd_args& a, const ba_cap_args& cp, int out_state,
+               int64_t B, int64_t D, int dtype, hipStream_t stream);
+int ba_cap_bwd(const bwd_dq_args& dq, const bwd_dq_args& dv,
+               const bwd_dq_args& dk, const ba_cap_args& cp, int64_t B,
+               int64_t D, int dtype, hipStream_t stream);
 
 // f(ba_td<T, D>{}) for the supported (head_dim, dtype) pairs, else 1002.
 template <typename T, int D_>

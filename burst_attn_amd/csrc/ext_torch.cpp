@@ -135,6 +135,19 @@ bool band_given(const c10::optional<int64_t>& band_lo,
   return band_lo.has_value();
 }
 
+// Logit soft-capping of a call: 0.0 is off and takes the call's path without
+// it; any other value goes to the *_softcap entry point, which refuses a
+// negative or non-finite one.  Never together with ids or a band (those
+// combinations have no kernel form yet).
+bool softcap_given(double softcap, const SegIds& seg, bool band) {
+  if (softcap == 0.0) return false;
+  TORCH_CHECK(!seg.q, "softcap and q_seg/kv_seg are not supported together "
+                      "yet");
+  TORCH_CHECK(!band, "softcap and band_lo/band_hi are not supported together "
+                     "yet");
+  return true;
+}
+
 // The pre-pass alone on [B, Sq] / [B, Sk] ids: the workspace as int32
 // words (layout: bahip_attn_seg_prepass).  For tests and measurements.
 at::Tensor attn_seg_prepass(const at::Tensor& q_seg, const at::Tensor& kv_seg) {
@@ -162,14 +175,27 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k,
                                  const c10::optional<at::Tensor>& q_seg,
                                  const c10::optional<at::Tensor>& kv_seg,
                                  const c10::optional<int64_t>& band_lo,
-                                 const c10::optional<int64_t>& band_hi) {
+                                 const c10::optional<int64_t>& band_hi,
+                                 double softcap) {
   check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
   const SegIds seg = seg_ids(q_seg, kv_seg, q, k);
+  const bool band = band_given(band_lo, band_hi, seg);
+  const bool capped = softcap_given(softcap, seg, band);
   auto o = at::empty({B, Sq, N, D}, q.options().dtype(at::kFloat));
   auto lse = at::empty({B, N, Sq}, q.options().dtype(at::kFloat));
-  if (band_given(band_lo, band_hi, seg)) {
+  if (capped) {
+    // the soft-capped forward transposes V in the kernel: no image workspace
+    BA_CALL(bahip_attn_fwd_softcap(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr<float>(),
+        lse.data_ptr<float>(), B, Sq, Sk, N, k.size(2), D, Strides3(q),
+        Strides3(k), Strides3(v), (float)softmax_scale, causal ? 1 : 0,
+        dtype_code(q), nullptr, 0, (float)softcap,
+        at::hip::getCurrentHIPStream().stream()));
+    return {o, lse};
+  }
+  if (band) {
     BA_CALL(bahip_attn_fwd_band(
         q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr<float>(),
         lse.data_ptr<float>(), B, Sq, Sk, N, k.size(2), D, Strides3(q),
@@ -231,7 +257,8 @@ void fwd_accum_call(void* asm_fn, const at::Tensor& q, const at::Tensor& k,
                     const c10::optional<at::Tensor>& q_seg = c10::nullopt,
                     const c10::optional<at::Tensor>& kv_seg = c10::nullopt,
                     const c10::optional<int64_t>& band_lo = c10::nullopt,
-                    const c10::optional<int64_t>& band_hi = c10::nullopt) {
+                    const c10::optional<int64_t>& band_hi = c10::nullopt,
+                    double softcap = 0.0) {
   check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
@@ -245,7 +272,18 @@ void fwd_accum_call(void* asm_fn, const at::Tensor& q, const at::Tensor& k,
   int64_t mls[2] = {m.stride(0), m.stride(1)};
   TORCH_CHECK(l.stride(0) == mls[0] && l.stride(1) == mls[1],
               "m/l stride mismatch");
-  if (band_given(band_lo, band_hi, seg)) {
+  const bool band = band_given(band_lo, band_hi, seg);
+  if (softcap_given(softcap, seg, band)) {
+    BA_CALL(bahip_attn_fwd_accum_softcap(
+        nullptr, q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Sq, Sk, N,
+        k.size(2), D, Strides3(q), Strides3(k), Strides3(v),
+        (float)softmax_scale, causal ? 1 : 0, dtype_code(q),
+        acc.data_ptr<float>(), m.data_ptr<float>(), l.data_ptr<float>(),
+        Strides3(acc), mls, carry_in ? 1 : 0, nullptr, 0, (float)softcap,
+        at::hip::getCurrentHIPStream().stream()));
+    return;
+  }
+  if (band) {
     BA_CALL(bahip_attn_fwd_accum_band(
         nullptr, q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Sq, Sk, N,
         k.size(2), D, Strides3(q), Strides3(k), Strides3(v),
@@ -275,9 +313,9 @@ void attn_fwd_accum(const at::Tensor& q, const at::Tensor& k,
                     bool carry_in, const c10::optional<at::Tensor>& q_seg,
                     const c10::optional<at::Tensor>& kv_seg,
                     const c10::optional<int64_t>& band_lo,
-                    const c10::optional<int64_t>& band_hi) {
+                    const c10::optional<int64_t>& band_hi, double softcap) {
   fwd_accum_call(nullptr, q, k, v, softmax_scale, causal, acc, m, l, carry_in,
-                 q_seg, kv_seg, band_lo, band_hi);
+                 q_seg, kv_seg, band_lo, band_hi, softcap);
 }
 
 // The empty carry-in state ("no key seen yet") written into acc [B,S,N,D],
@@ -361,7 +399,7 @@ void attn_bwd_accum(const at::Tensor& dout, const at::Tensor& q,
                     const c10::optional<at::Tensor>& q_seg,
                     const c10::optional<at::Tensor>& kv_seg,
                     const c10::optional<int64_t>& band_lo,
-                    const c10::optional<int64_t>& band_hi) {
+                    const c10::optional<int64_t>& band_hi, double softcap) {
   check_qkv(dout, "dout");
   check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
@@ -384,7 +422,19 @@ void attn_bwd_accum(const at::Tensor& dout, const at::Tensor& q,
   int64_t ds[2] = {delta.stride(0), delta.stride(1)};
   int64_t ls[2] = {lse.stride(0), lse.stride(1)};
   auto stream = at::hip::getCurrentHIPStream().stream();
-  if (band_given(band_lo, band_hi, seg)) {
+  const bool band = band_given(band_lo, band_hi, seg);
+  if (softcap_given(softcap, seg, band)) {
+    BA_CALL(bahip_attn_bwd_softcap(
+        dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+        delta.data_ptr<float>(), lse.data_ptr<float>(), dq.data_ptr<float>(),
+        dk.data_ptr<float>(), dv.data_ptr<float>(), B, Sq, Sk, N, k.size(2), D,
+        Strides3(dout), Strides3(q), Strides3(k), Strides3(v), ds, ls,
+        Strides3(dq), Strides3(dk), Strides3(dv), (float)softmax_scale,
+        causal ? 1 : 0, deterministic ? 1 : 0, dtype_code(q), (float)softcap,
+        stream));
+    return;
+  }
+  if (band) {
     BA_CALL(bahip_attn_bwd_band(
         dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
         delta.data_ptr<float>(), lse.data_ptr<float>(), dq.data_ptr<float>(),
@@ -413,7 +463,8 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
                                  const c10::optional<at::Tensor>& q_seg,
                                  const c10::optional<at::Tensor>& kv_seg,
                                  const c10::optional<int64_t>& band_lo,
-                                 const c10::optional<int64_t>& band_hi) {
+                                 const c10::optional<int64_t>& band_hi,
+                                 double softcap) {
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
   // zero-filled: the kernels accumulate, so this equals fresh outputs
@@ -423,7 +474,8 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
   auto dk = at::zeros({B, Sk, Nk, D}, q.options().dtype(at::kFloat));
   auto dv = at::zeros({B, Sk, Nk, D}, q.options().dtype(at::kFloat));
   attn_bwd_accum(dout, q, k, v, delta, lse, softmax_scale, causal,
-                 deterministic, dq, dk, dv, q_seg, kv_seg, band_lo, band_hi);
+                 deterministic, dq, dk, dv, q_seg, kv_seg, band_lo, band_hi,
+                 softcap);
   return {dq, dk, dv};
 }
 
@@ -490,14 +542,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("softmax_scale"),
         py::arg("causal"), py::arg("q_seg") = py::none(),
         py::arg("kv_seg") = py::none(), py::arg("band_lo") = py::none(),
-        py::arg("band_hi") = py::none());
+        py::arg("band_hi") = py::none(), py::arg("softcap") = 0.0);
   m.def("attn_fwd_accum", &attn_fwd_accum,
         "carry-in accumulator fwd tile (in-kernel LSE merge)", py::arg("q"),
         py::arg("k"), py::arg("v"), py::arg("softmax_scale"),
         py::arg("causal"), py::arg("acc"), py::arg("m"), py::arg("l"),
         py::arg("carry_in"), py::arg("q_seg") = py::none(),
         py::arg("kv_seg") = py::none(), py::arg("band_lo") = py::none(),
-        py::arg("band_hi") = py::none());
+        py::arg("band_hi") = py::none(), py::arg("softcap") = 0.0);
   m.def("attn_fwd_state_init", &attn_fwd_state_init,
         "write the empty carry-in state (no key seen yet) into acc, m, l");
   m.def("attn_seg_prepass", &attn_seg_prepass,
@@ -520,14 +572,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("delta"), py::arg("lse"), py::arg("softmax_scale"),
         py::arg("causal"), py::arg("deterministic"),
         py::arg("q_seg") = py::none(), py::arg("kv_seg") = py::none(),
-        py::arg("band_lo") = py::none(), py::arg("band_hi") = py::none());
+        py::arg("band_lo") = py::none(), py::arg("band_hi") = py::none(),
+        py::arg("softcap") = 0.0);
   m.def("attn_bwd_accum", &attn_bwd_accum,
         "bwd tile accumulating into fp32 dq/dk/dv views", py::arg("dout"),
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("delta"),
         py::arg("lse"), py::arg("softmax_scale"), py::arg("causal"),
         py::arg("deterministic"), py::arg("dq"), py::arg("dk"), py::arg("dv"),
         py::arg("q_seg") = py::none(), py::arg("kv_seg") = py::none(),
-        py::arg("band_lo") = py::none(), py::arg("band_hi") = py::none());
+        py::arg("band_lo") = py::none(), py::arg("band_hi") = py::none(),
+        py::arg("softcap") = 0.0);
   m.def("mfma_probe", &mfma_probe, "32x32x16 MFMA layout probe");
   m.def("tr16_probe", &tr16_probe, "ds_read_tr16_b64 semantics probe");
   m.def("attn_fwd_asm_load", &attn_fwd_asm_load,

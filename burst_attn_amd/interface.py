@@ -49,6 +49,15 @@ tile provider, and a round with no visible pair computes nothing (its
 communication is unchanged).  Without a window neither the provider calls
 nor the kernels change.  A window together with ``segment_ids`` is refused.
 
+Logit soft-capping: the trailing keyword ``softcap`` (the flash-attn
+convention, ``0.0`` = off) replaces every score ``s = q.k * softmax_scale`` by
+``softcap * tanh(s / softcap)`` before the softmax, in the forward and the
+backward kernels of every round.  The cap is a Python float that every rank
+knows: nothing new travels the ring, and each round hands the tile provider
+``softcap=`` so that all rounds cap alike and the in-kernel merge holds.
+Without a cap the provider calls carry no such keyword.  A cap together with
+``segment_ids`` or an effective window is refused.
+
 The two causal load-balancing layouts (see oracle/partition.py) run the
 same code: ``OpBurstAttn`` (zigzag: rank r holds global chunks [r] and
 [2W-1-r]) and ``OpBurstAttnStrip`` (striped: token t on rank t mod W) only
@@ -327,6 +336,33 @@ def _check_masks_for_head_dim(q, segment_ids, window):
         )
 
 
+def _check_softcap(softcap, segment_ids, window):
+    """The cap as a float, 0.0 for "off"."""
+    if (isinstance(softcap, bool) or not isinstance(softcap, (int, float))
+            or not math.isfinite(softcap) or softcap < 0):
+        raise ValueError(
+            "softcap must be 0.0 (off) or a positive finite number, got "
+            f"{softcap!r}"
+        )
+    if softcap > 0:
+        other = ("segment_ids" if segment_ids is not None
+                 else "window_size" if window is not None else None)
+        if other:
+            raise ValueError(
+                f"softcap and {other} are not supported together yet"
+            )
+    return float(softcap)
+
+
+def _op_args(ids, window, softcap):
+    """The trailing arguments of the two ops: the ids always, the window and
+    the cap only when given, so that a call without them applies the op with
+    the argument list it had before they existed."""
+    if softcap > 0:
+        return (ids, None, softcap)  # never with a window
+    return (ids,) if window is None else (ids, window)
+
+
 def burst_attn_func(
     q: torch.Tensor,
     k: torch.Tensor,
@@ -341,15 +377,16 @@ def burst_attn_func(
     *,
     segment_ids: torch.Tensor = None,
     window_size=None,
+    softcap: float = 0.0,
 ):
     _check_heads(q, k, v)
     window = _check_window(window_size, causal, segment_ids)
     _check_masks_for_head_dim(q, segment_ids, window)
+    softcap = _check_softcap(softcap, segment_ids, window)
     return OpBurstAttn.apply(
         q, k, v, softmax_scale, flash, causal, optimize_bwd_comm,
         deterministic, process_group, double_group,
-        _check_segment_ids(segment_ids, q),
-        *(() if window is None else (window,)),
+        *_op_args(_check_segment_ids(segment_ids, q), window, softcap),
     )
 
 
@@ -367,28 +404,32 @@ def burst_attn_func_striped(
     *,
     segment_ids: torch.Tensor = None,
     window_size=None,
+    softcap: float = 0.0,
 ):
     _check_heads(q, k, v)
     window = _check_window(window_size, causal, segment_ids)
     _check_masks_for_head_dim(q, segment_ids, window)
+    softcap = _check_softcap(softcap, segment_ids, window)
     return OpBurstAttnStrip.apply(
         q, k, v, softmax_scale, flash, causal, optimize_bwd_comm,
         deterministic, process_group, double_group,
-        _check_segment_ids(segment_ids, q),
-        *(() if window is None else (window,)),
+        *_op_args(_check_segment_ids(segment_ids, q), window, softcap),
     )
 
 
 def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
                   causal=False, optimize_bwd_comm=False, deterministic=False,
                   process_group=None, double_group=[None, None],
-                  segment_ids=None, window=None):
+                  segment_ids=None, window=None, softcap=0.0):
     """Forward of both layouts: q stays, {k, v} travel the ring (with the
     kv ids, when there are segment ids).  With a window every round is the
-    sub-tiles of ``window_tiles``, merged into a state that starts empty."""
+    sub-tiles of ``window_tiles``, merged into a state that starts empty.
+    With a cap every round's tile call carries it."""
     _check_flash_arg(flash)
     ctx.segment_ids = ids = segment_ids
     ctx.window = window
+    ctx.softcap = softcap
+    cap = {"softcap": softcap} if softcap > 0 else {}
     ctx.dq_group = double_group
     if isinstance(double_group[0], tuple):
         # [(group, dq_group), (group2, dq_group2)] — separate backward dq
@@ -437,7 +478,8 @@ def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
         else:
             seg = {} if ids is None else {"seg": (ids[:, qw], kv_ids[:, kw])}
             state = P.fwd_accum(state, q[:, qw], k[:, kw], v[:, kw], scale,
-                                tile_causal, row_offset=qw.start or 0, **seg)
+                                tile_causal, row_offset=qw.start or 0, **seg,
+                                **cap)
         if r != W:
             recv, comm_bufs = _record_stream(*comm_bufs), payload
             k, v = recv[:2]
@@ -495,6 +537,7 @@ def _ring_backward(layout, ctx, grad_output):
     ids = ctx.segment_ids
     q_ids = None if ids is None else replicate(ids)
     window = ctx.window
+    cap = {"softcap": ctx.softcap} if ctx.softcap > 0 else {}
     P = get_tile_provider()
     scale, causal = ctx.softmax_scale, ctx.causal
     grad_output = grad_output.contiguous()
@@ -562,6 +605,7 @@ def _ring_backward(layout, ctx, grad_output):
                 delta[:, :, qw], lse[:, :, qw], scale, tile_causal,
                 ctx.deterministic, tgt[:, qw], dk[:, kw], dv[:, kw],
                 **({} if ids is None else {"seg": (q_ids[:, qw], ids[:, kw])}),
+                **cap,
             )
         if r != W:
             recv, read_bufs = _record_stream(*read_bufs), payload
@@ -580,7 +624,8 @@ def _ring_backward(layout, ctx, grad_output):
     return (
         dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype),
         None, None, None, None, None, None, None, None,
-        *(() if window is None else (None,)),
+        # one None per trailing argument of _op_args beyond the ids
+        *((None, None) if cap else () if window is None else (None,)),
     )
 
 

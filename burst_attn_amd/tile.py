@@ -65,6 +65,15 @@ finalizing it gives ``o = 0``, ``lse = -inf``, and ``fwd_accum`` merges into
 it at any ``row_offset``; a ring whose first tile does not cover every row
 starts from it.
 
+Logit soft-capping: the same four methods take an optional keyword
+``softcap``, a positive Python float.  Every score ``s = q.k * scale`` then
+becomes ``softcap * tanh(s / softcap)`` before the softmax; ``causal`` applies
+as without it, ``lse`` is the log-sum-exp of the capped scores, and the state
+of ``fwd_accum`` keeps its contract, so rounds merge as long as every round
+of a ring passes the same value.  ``None`` (and ``0.0``, the flash-attn
+"off") is the call without it.  ``softcap`` with ``seg`` or ``band`` is
+refused.  A caller without a cap passes no ``softcap`` keyword at all.
+
 The default provider is the gfx950 HIP extension and FAILS LOUDLY if the
 extension is missing on a GPU machine — there is no CPU/eager fallback in
 the product path.  Tests may inject an oracle-backed provider via
@@ -121,29 +130,42 @@ class HipTileProvider:
         lo, hi = band
         return {"band_lo": int(lo), "band_hi": int(hi)}
 
-    def fwd(self, q, k, v, scale, causal, seg=None, band=None):
+    @staticmethod
+    def _cap_kw(softcap, seg, band):
+        """The extension's keyword of a ``softcap``; none without one."""
+        if softcap is None or softcap == 0.0:
+            return {}
+        if seg is not None or band is not None:
+            raise RuntimeError(
+                "softcap and " + ("seg" if seg is not None else "band")
+                + " are not supported together yet")
+        return {"softcap": float(softcap)}
+
+    def fwd(self, q, k, v, scale, causal, seg=None, band=None, softcap=None):
         q_seg, kv_seg = seg if seg is not None else (None, None)
         return self._ext.attn_fwd(q, k, v, float(scale), bool(causal),
-                                  q_seg, kv_seg, **self._band_kw(band))
+                                  q_seg, kv_seg, **self._band_kw(band),
+                                  **self._cap_kw(softcap, seg, band))
 
     def bwd_preprocess(self, o, do, out=None):
         return self._ext.attn_bwd_preprocess(o, do, out)
 
     def bwd(self, do, q, k, v, delta, lse, scale, causal, deterministic,
-            seg=None, band=None):
+            seg=None, band=None, softcap=None):
         q_seg, kv_seg = seg if seg is not None else (None, None)
         return self._ext.attn_bwd(
             do, q, k, v, delta, lse, float(scale), bool(causal),
             bool(deterministic), q_seg, kv_seg, **self._band_kw(band),
+            **self._cap_kw(softcap, seg, band),
         )
 
     def bwd_accum(self, do, q, k, v, delta, lse, scale, causal, deterministic,
-                  dq, dk, dv, seg=None, band=None):
+                  dq, dk, dv, seg=None, band=None, softcap=None):
         q_seg, kv_seg = seg if seg is not None else (None, None)
         self._ext.attn_bwd_accum(
             do, q, k, v, delta, lse, float(scale), bool(causal),
             bool(deterministic), dq, dk, dv, q_seg, kv_seg,
-            **self._band_kw(band),
+            **self._band_kw(band), **self._cap_kw(softcap, seg, band),
         )
 
     def merge(self, o, lse, o_i, lse_i):
@@ -154,17 +176,19 @@ class HipTileProvider:
     # running max, l fp32 [B,N,S] running sum) over the rank's FULL chunk;
     # row_offset targets the zigzag-half / striped-shift row windows.
     def fwd_accum(self, state, q, k, v, scale, causal, row_offset=0, seg=None,
-                  band=None):
+                  band=None, softcap=None):
+        cap_kw = self._cap_kw(softcap, seg, band)
         # the .s-built module carries the D=128 production variants only,
-        # and no segment or band form: with either the in-binary kernel runs
+        # and no segment, band or soft-capped form: with any of them the
+        # in-binary kernel runs
         if (self._asm_fwd and q.shape[3] == 128 and seg is None
-                and band is None):
+                and band is None and not cap_kw):
             accum = self._ext.attn_fwd_accum_asm
-        elif seg is not None or band is not None:
+        elif seg is not None or band is not None or cap_kw:
             q_seg, kv_seg = seg if seg is not None else (None, None)
             accum = functools.partial(self._ext.attn_fwd_accum,
                                       q_seg=q_seg, kv_seg=kv_seg,
-                                      **self._band_kw(band))
+                                      **self._band_kw(band), **cap_kw)
         else:
             accum = self._ext.attn_fwd_accum
         if state is None:

@@ -106,6 +106,28 @@
  *     variant; BA_BWD_FUSED=1/2, BA_BWD_DK_FLIP=1, BA_DQ_PIPE=1.  A knob value
  *     outside its set is BAHIP_ERR_BAD_KNOB as everywhere.  Any other D
  *     (96 included) returns BAHIP_ERR_UNSUPPORTED.
+ *   - softcap (logit soft-capping, the flash-attn `softcap` argument): the
+ *     *_softcap entry points take a float softcap before stream.  With
+ *     softcap > 0 pair (i, j) gets the score
+ *     softcap * tanh(q_i.k_j * softmax_scale / softcap) in place of
+ *     q_i.k_j * softmax_scale; the causal / rectangular rule of the call then
+ *     applies as without it.  lse is the natural-log sum-exp of the capped
+ *     scores, o, dq, dk and dv are those of softmax over the capped scores
+ *     times V; the state contract, finalize, state init and the preprocess
+ *     are unchanged, and a ring caps every round with the same value.
+ *     softcap == 0 is exactly the entry point without it (image form, module
+ *     kernel and knobs included); softcap < 0 or non-finite returns
+ *     BAHIP_ERR_SOFTCAP and launches nothing.  Supported at D = 64, 128 and
+ *     256 (each head_dim's own kernel set in a soft-capped form), fp16 and
+ *     bf16, GQA, strided slices, and as bitwise deterministic in the backward
+ *     as the plain kernels.  A cap is supported by the default forward
+ *     variant and the default backward plan only: another BA_FWD_* selection,
+ *     BA_BWD_FUSED=1/2, BA_BWD_DK_FLIP=1 or BA_DQ_PIPE=1 returns
+ *     BAHIP_ERR_UNSUPPORTED naming the knob and softcap, nothing launched.
+ *     The forward with a cap transposes V in the kernel whatever BA_FWD_VT
+ *     says (its V^T workspace argument is ignored) and never uses
+ *     hip_function.  A cap together with segment ids or a band has no entry
+ *     point.
  *   - stream is a hipStream_t.
  * Returns 0 on success; nonzero = error.  Every nonzero return sets the
  * calling thread's bahip_last_error() message and every success clears it.
@@ -136,6 +158,8 @@ extern "C" {
 #define BAHIP_ERR_SEGMENT_IDS 1006    /* one of q_seg / kv_seg is null */
 
 #define BAHIP_ERR_BAND 1007           /* band_lo > band_hi */
+
+#define BAHIP_ERR_SOFTCAP 1008        /* softcap negative or not finite */
 
 const char* bahip_last_error(void);
 
@@ -378,6 +402,40 @@ int bahip_attn_bwd_band(
     const int64_t dv_strides[3],
     float softmax_scale, int causal, int deterministic, int dtype,
     int64_t band_lo, int64_t band_hi, void* stream);
+
+/* ---- softcap (see "softcap" above) --------------------------------------
+ * bahip_attn_fwd_gqa_ws, bahip_attn_fwd_accum_gqa_ws and bahip_attn_bwd_gqa
+ * with logit soft-capping. */
+int bahip_attn_fwd_softcap(
+    const void* q, const void* k, const void* v,
+    float* o, float* lse,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3],
+    const int64_t k_strides[3],
+    const int64_t v_strides[3],
+    float softmax_scale, int causal, int dtype,
+    void* workspace, int64_t workspace_bytes, float softcap, void* stream);
+int bahip_attn_fwd_accum_softcap(
+    void* hip_function,
+    const void* q, const void* k, const void* v,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    float* acc, float* m, float* l, const int64_t acc_strides[3],
+    const int64_t ml_strides[2], int carry_in,
+    void* workspace, int64_t workspace_bytes, float softcap, void* stream);
+int bahip_attn_bwd_softcap(
+    const void* dout, const void* q, const void* k, const void* v,
+    const float* delta, const float* lse,
+    float* dq, float* dk, float* dv,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t do_strides[3], const int64_t q_strides[3],
+    const int64_t k_strides[3], const int64_t v_strides[3],
+    const int64_t delta_strides[2], const int64_t lse_strides[2],
+    const int64_t dq_strides[3], const int64_t dk_strides[3],
+    const int64_t dv_strides[3],
+    float softmax_scale, int causal, int deterministic, int dtype,
+    float softcap, void* stream);
 
 /* The empty state, "no key seen yet", over [B, S] rows of a carry-in state
  * (acc strided {b,s,h}, m/l strided {b,h}, as in bahip_attn_fwd_accum):
