@@ -33,6 +33,13 @@ its ratio to the dense causal row and the ideal ratio: the (256-row block,
 under the causal triangle, counted with the arithmetic of
 csrc/band_support.h.  TFLOPS of the window rows count the visible pairs only.
 
+Block-sparse attention:
+  python benchmarks/sweep.py --configs blocksparse
+runs, at --seq (65536), dense causal and then causal under a local-plus-
+strided block mask (block 64: the last 32 key blocks plus every 16th, 1/8 of
+the causal blocks at 65536), and reports the ideal tile ratio and the
+pre-pass time next to the measured ratios.
+
 Logit soft-capping:
   python benchmarks/sweep.py --softcap 30
 runs, at --seq (65536), dense causal and then the same call with
@@ -225,6 +232,72 @@ def bench_window(args, s, n, nk, d, window, dense, steps, warmup):
     }
 
 
+def local_strided_mask(s, bs=64, local=32, stride=16):
+    """[1, 1, s/bs, s/bs] bool: query block i sees key block j <= i iff
+    i - j < local or j % stride == 0 (a local band plus strided "global"
+    columns); 1/8 of the causal blocks at s = 65536 with the defaults."""
+    i = torch.arange(s // bs)
+    m = (i[:, None] >= i[None, :]) & ((i[:, None] - i[None, :] < local)
+                                      | (i[None, :] % stride == 0))
+    return m[None, None]
+
+
+def bench_blocksparse(args, s, n, nk, d, dense, steps, warmup):
+    """Causal forward and forward+backward under the local-plus-strided block
+    mask, next to the dense causal row `dense` of the same run, the ideal
+    ratio (listed (256-row block, 64-row tile) pairs over all causal ones) and
+    the pre-pass alone."""
+    from burst_attn_amd import burst_attn_func
+    from burst_attn_amd._ext import load_extension
+
+    bs = 64
+    dtype = torch.float16 if args.dtype == "fp16" else torch.bfloat16
+    g = torch.Generator().manual_seed(1000)
+    mk = lambda h=n: torch.randn(1, s, h, d, generator=g).to(dtype).cuda()
+    q, k, v, do = mk(), mk(nk), mk(nk), mk()
+    m = local_strided_mask(s, bs)
+    md = m.cuda()
+    kw = {"block_mask": md, "block_size": bs}
+
+    def fwd():
+        with torch.no_grad():
+            burst_attn_func(q, k, v, None, "cuda", True, **kw)
+
+    def fwdbwd():
+        qg, kg, vg = (t.detach().requires_grad_() for t in (q, k, v))
+        o = burst_attn_func(qg, kg, vg, None, "cuda", True, **kw)
+        torch.autograd.grad(o, (qg, kg, vg), do)
+
+    t_f = timeit(fwd, steps, warmup)
+    t_fb = timeit(fwdbwd, steps, warmup)
+    ext, m8 = load_extension(), md.to(torch.uint8)
+    t_pre = timeit(lambda: ext.attn_blk_prepass(m8, bs, s, s, True), 20, 3)
+    # the forward's one host copy of the slab (its "no set block" test)
+    t_host = timeit(lambda: m8.cpu(), 20, 3)
+    nb = s // bs
+    blocks = int(m.sum())
+    # a workgroup's 256 rows are four 64-row blocks; its list holds a 64-key
+    # tile iff one of them has the block set
+    listed = int(m[0, 0].view(nb // 4, 4, nb).any(1).sum())
+    causal_tiles = sum(4 * b + 4 for b in range(nb // 4))
+    f = 4.0 * blocks * bs * bs * n * d  # set blocks, diagonal ones in full
+    return {
+        "method": "burst_blocksparse", "b": 1, "s": s, "n": n, "nk": nk, "d": d,
+        "causal": True, "block_size": bs, "pattern": "local32+stride16",
+        "wsize": 1, "dtype": args.dtype,
+        "block_density": round(blocks / (nb * (nb + 1) / 2), 4),
+        "ideal_tile_ratio": round(listed / causal_tiles, 4),
+        "fwd_ms": round(t_f * 1e3, 2),
+        "fwd_ratio_to_causal": round(t_f * 1e3 / dense["fwd_ms"], 4),
+        "fwd_tflops_per_gpu": round(f / t_f / 1e12, 2),
+        "fwdbwd_ms": round(t_fb * 1e3, 2),
+        "fwdbwd_ratio_to_causal": round(t_fb * 1e3 / dense["fwdbwd_ms"], 4),
+        "fwdbwd_tflops_per_gpu": round(3.5 * f / t_fb / 1e12, 2),
+        "prepass_us": round(t_pre * 1e6, 1),
+        "slab_host_copy_us": round(t_host * 1e6, 1),
+    }
+
+
 def bench_seg_prepass(args, s, doc_len, steps, warmup):
     """The segment pre-pass alone (both side pairs, as the backward runs
     it; the forward runs half of it)."""
@@ -351,7 +424,7 @@ def main():
     p = argparse.ArgumentParser()
     p.add_argument("--configs",
                    choices=["quick", "ring", "batch", "single", "naive", "gqa",
-                            "packed"],
+                            "packed", "blocksparse"],
                    default="quick")
     p.add_argument("--steps", type=int, default=3)
     p.add_argument("--warmup", type=int, default=1)
@@ -480,6 +553,15 @@ def main():
                                  args.warmup))
         for sp in (65536, 1048576):
             rows.append(bench_seg_prepass(args, sp, doc_lens[0], 20, 3))
+
+    elif args.configs == "blocksparse":
+        if world != 1:
+            p.error("--configs blocksparse is a one-GPU config")
+        dense = bench_burst(args, 1, args.seq, n, d, True, False, False,
+                            args.steps, args.warmup, nk)
+        rows.append(dense)
+        rows.append(bench_blocksparse(args, args.seq, n, nk, d, dense,
+                                      args.steps, args.warmup))
 
     if rank == 0:
         with open(args.out, "a") as f:

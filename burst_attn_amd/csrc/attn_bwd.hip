@@ -78,7 +78,10 @@ constexpr int KVBLK = 64;
 // ba_band_args = the band form.  One ba_cap_args = the soft-capped form
 // (attn_common.h): t = tanh(.) recomputed from the raw score,
 // p = exp2(t * c2cap - lse2), dS = p * (dP - delta) * (1 - t^2) * scale; the
-// mask stays on the exponent, where the plain kernel has it.
+// mask stays on the exponent, where the plain kernel has it.  One ba_blk_args
+// = the block form (attn_common.h, blk_support.h): the loop runs over the
+// workgroup's list of kv tiles, a wave computes a tile iff the entry's bit
+// says so, and the element mask is the plain one.
 template <typename T, int D, int DQP = 0, typename... SEG>
 __global__ __launch_bounds__(512) void bwd_dq_kernel(
     const T* __restrict__ dout, const T* __restrict__ q,
@@ -96,10 +99,14 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
   using frag = typename MT::frag;
   constexpr bool HAS_BAND = ba_pack_is<ba_band_args, SEG...>;
   constexpr bool HAS_CAP = ba_pack_is<ba_cap_args, SEG...>;
-  constexpr bool HAS_SEG = sizeof...(SEG) != 0 && !HAS_BAND && !HAS_CAP;
+  constexpr bool HAS_BLK = ba_pack_is<ba_blk_args, SEG...>;
+  constexpr bool HAS_SEG =
+      sizeof...(SEG) != 0 && !HAS_BAND && !HAS_CAP && !HAS_BLK;
   constexpr bool HAS_MASK = HAS_SEG || HAS_BAND;
   static_assert(!(HAS_MASK || HAS_CAP) || (sizeof...(SEG) == 1 && DQP == 0),
                 "segment ids / band / softcap: the default dq kernel");
+  static_assert(!HAS_BLK || (DQP == 0 && KVBLK == BA_BLK_TILE),
+                "block masks: the default dq kernel, tiles of blk_support.h");
   ba_cap_args cp = {0.f, 0.f};
   if constexpr (HAS_CAP) cp = ba_cap_of(seg...);
   // band form: the band is the whole mask (the launcher folded causal in)
@@ -200,8 +207,24 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
     trange.y = r.hi;
     if (trange.x >= trange.y) return;  // workgroup-uniform, no barrier yet
   }
-  const int t_first = HAS_MASK ? trange.x : 0;
-  const int nt = HAS_MASK ? trange.y : nt_shape;
+  // block form: t is a position in the workgroup's list of kv tiles; e_cur is
+  // the entry of the tile being computed, e_nxt the one after it
+  const uint32_t* blst = nullptr;
+  uint32_t e_cur = 0, e_nxt = 0;
+  int wave_u = 0;
+  if constexpr (HAS_BLK) {
+    const ba_blk_args ba = ba_blk_of(seg...);
+    const int64_t li = ba_blk_list_index(ba, b, nkv);
+    trange.x = 0;
+    trange.y = ba_blk_word(ba.cnt, li);
+    if (trange.y <= 0) return;  // workgroup-uniform, no barrier yet
+    blst = ba.list + li * ba.stride;
+    e_cur = ba_blk_word(blst, 0);
+    e_nxt = ba_blk_word(blst, min(1, trange.y - 1));
+    wave_u = __builtin_amdgcn_readfirstlane(wave);
+  }
+  const int t_first = (HAS_MASK || HAS_BLK) ? trange.x : 0;
+  const int nt = (HAS_MASK || HAS_BLK) ? trange.y : nt_shape;
 
   auto issue_loads = [&](int tile, u32x4_t* kreg, u32x4_t* vreg) {
     const int kv0 = tile * KVBLK;
@@ -231,7 +254,8 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
 
   {
     u32x4_t kreg[PT], vreg[PT];
-    issue_loads(t_first, kreg, vreg);
+    issue_loads(HAS_BLK ? (int)(e_cur & BA_BLK_TILE_MASK) : t_first, kreg,
+                vreg);
     write_lds(0, kreg, vreg);
     __syncthreads();
   }
@@ -240,13 +264,20 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
 
   int cur = 0;
   for (int t = t_first; t < nt; ++t) {
-    const int kv0 = t * KVBLK;
+    const int kv0 = (HAS_BLK ? (int)(e_cur & BA_BLK_TILE_MASK) : t) * KVBLK;
     const bool has_next = (t + 1) < nt;
     u32x4_t kreg[PT], vreg[PT];
-    if (has_next) issue_loads(t + 1, kreg, vreg);
+    if (has_next)
+      issue_loads(HAS_BLK ? (int)(e_nxt & BA_BLK_TILE_MASK) : t + 1, kreg,
+                  vreg);
 
     bool active, seg_mask = false;
-    if constexpr (HAS_SEG) {
+    if constexpr (HAS_BLK) {
+      // the entry's bit of this wave; the causal tile test is folded into it
+      active = (e_cur >> (BA_BLK_TILE_BITS + wave_u)) & 1;
+      e_cur = e_nxt;
+      e_nxt = ba_blk_word(blst, min(t + 2, nt - 1));
+    } else if constexpr (HAS_SEG) {
       // segment form: the tile's (min, max) ids against the wave's
       const int2 mm = tmm[t];
       seg_mask = !(mm.x == mm.y && wq_min == wq_max && mm.x == wq_min);
@@ -378,7 +409,9 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
 // tanh needs the raw score, so -lse*log2e/c2cap leaves the S accumulator for
 // one of its own (the same one-MFMA broadcast of the row constant, 16 more
 // registers), and p = exp2((t + that) * c2cap), dS = p * dP' * (1 - t^2) *
-// scale with dP' = dP - delta from the fold as before.
+// scale with dP' = dP - delta from the fold as before.  One ba_blk_args = the
+// block form: the flattened stream walks the workgroup's list of q tiles once
+// per group member, wrapping to the list's head for the next member.
 template <typename T, int D, int MODE, int QBLK = 64, int GQA = 0,
           typename... SEG>
 __global__ __launch_bounds__(512) void bwd_dkv_kernel(
@@ -397,9 +430,13 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
   using frag = typename MT::frag;
   constexpr bool HAS_BAND = ba_pack_is<ba_band_args, SEG...>;
   constexpr bool HAS_CAP = ba_pack_is<ba_cap_args, SEG...>;
-  constexpr bool HAS_SEG = sizeof...(SEG) != 0 && !HAS_BAND && !HAS_CAP;
+  constexpr bool HAS_BLK = ba_pack_is<ba_blk_args, SEG...>;
+  constexpr bool HAS_SEG =
+      sizeof...(SEG) != 0 && !HAS_BAND && !HAS_CAP && !HAS_BLK;
   constexpr bool HAS_MASK = HAS_SEG || HAS_BAND;
   static_assert(!HAS_CAP || QBLK == 64, "softcap: the default q tile");
+  static_assert(!HAS_BLK || QBLK == BA_BLK_TILE,
+                "block masks: q tiles of blk_support.h");
   ba_cap_args cp = {0.f, 0.f};
   if constexpr (HAS_CAP) cp = ba_cap_of(seg...);
   static_assert(!HAS_MASK || (sizeof...(SEG) == 1 && QBLK == BA_SEG_TILE &&
@@ -505,8 +542,26 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
     trange.y = r.hi;
     if (trange.x >= trange.y) return;  // workgroup-uniform, no barrier yet
   }
-  const int t0 = HAS_MASK ? trange.x : t0_shape;
-  const int nt = HAS_MASK ? trange.y : nt_shape;
+  // block form: t is a position in the workgroup's list of q tiles, the same
+  // list for every member of the group (the mask's heads are KV heads, n
+  // here); e_cur is the entry of the tile being computed, e_nxt the one after
+  // it in the flattened stream, which wraps to the list's head
+  const uint32_t* blst = nullptr;
+  uint32_t e_cur = 0, e_nxt = 0;
+  int wave_u = 0;
+  if constexpr (HAS_BLK) {
+    const ba_blk_args ba = ba_blk_of(seg...);
+    const int64_t li = ba_blk_list_index(ba, b, n);
+    trange.x = 0;
+    trange.y = ba_blk_word(ba.cnt, li);
+    if (trange.y <= 0) return;  // workgroup-uniform, no barrier yet
+    blst = ba.list + li * ba.stride;
+    e_cur = ba_blk_word(blst, 0);
+    e_nxt = ba_blk_word(blst, trange.y > 1 ? 1 : 0);
+    wave_u = __builtin_amdgcn_readfirstlane(wave);
+  }
+  const int t0 = (HAS_MASK || HAS_BLK) ? trange.x : t0_shape;
+  const int nt = (HAS_MASK || HAS_BLK) ? trange.y : nt_shape;
 
   // per-lane lse*log2e and delta for both subtiles of a tile (l2[qs] =
   // {lse2, delta}), loaded straight from global — clamped, branchless
@@ -559,7 +614,8 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
   float2 l2c[QBLK / 32];
   {
     u32x4_t qreg[PT], greg[PT];
-    issue_loads(0, t0, qreg, greg, l2c);
+    issue_loads(0, HAS_BLK ? (int)(e_cur & BA_BLK_TILE_MASK) : t0, qreg, greg,
+                l2c);
     write_lds(0, qreg, greg);
     __syncthreads();
   }
@@ -573,16 +629,28 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
   int cur = 0;
   for (int g = 0; g < ng; ++g)
   for (int t = t0; t < nt; ++t) {
-    const int q0 = t * QBLK;
+    const int q0 = (HAS_BLK ? (int)(e_cur & BA_BLK_TILE_MASK) : t) * QBLK;
     const bool last_t = (t + 1) >= nt;
     const bool has_next = !last_t || (GQA && g + 1 < ng);
     u32x4_t qreg[PT], greg[PT];
     float2 l2n[QBLK / 32] = {};
     if (has_next)
-      issue_loads(last_t ? g + 1 : g, last_t ? t0 : t + 1, qreg, greg, l2n);
+      issue_loads(last_t ? g + 1 : g,
+                  HAS_BLK  ? (int)(e_nxt & BA_BLK_TILE_MASK)
+                  : last_t ? t0
+                           : t + 1,
+                  qreg, greg, l2n);
 
     bool active, seg_mask = false;
-    if constexpr (HAS_SEG) {
+    if constexpr (HAS_BLK) {
+      // the entry's bit of this wave; the causal tile test is folded into it
+      active = (e_cur >> (BA_BLK_TILE_BITS + wave_u)) & 1;
+      e_cur = e_nxt;
+      int j = t + 2;  // the position after the next, wrapped (nt may be 1)
+      if (j >= nt) j -= nt;
+      if (j >= nt) j = 0;
+      e_nxt = ba_blk_word(blst, j);
+    } else if constexpr (HAS_SEG) {
       // segment form: the q tile's (min, max) ids against the wave's kv ids
       const int2 mm = tmm[t];
       seg_mask = !(mm.x == mm.y && wk_min == wk_max && mm.x == wk_min);
@@ -1287,7 +1355,7 @@ static int bwd_entry(
     const int64_t dqs[3], const int64_t dks[3], const int64_t dvs[3],
     float scale, int causal, int deterministic, int dtype, void* stream,
     const bwd_seg_call* seg, const bwd_band_call* band = nullptr,
-    float softcap = 0.f) {
+    float softcap = 0.f, const ba_blk_call* blk = nullptr) {
   (void)deterministic;  // only atomic6 is not deterministic by construction
   if (causal && Sq != Sk)
     return ba_fail(BAHIP_ERR_CAUSAL_SHAPE,
@@ -1335,10 +1403,10 @@ static int bwd_entry(
   if (D == BA_D256) {
     // head_dim 256: the default plan's three kernels in their one-wave-per-
     // SIMD form (attn_d256.h), the plain call only
-    if (seg || band)
+    if (seg || band || blk)
       return ba_fail(BAHIP_ERR_UNSUPPORTED,
                      "head_dim 256 does not support %s (plain calls only)",
-                     seg ? "segment ids" : "a band");
+                     seg ? "segment ids" : band ? "a band" : "a block mask");
     const ba_seg_verdict sv = ba_seg_bwd_support(kn);
     if (sv.knob)
       return ba_fail(BAHIP_ERR_UNSUPPORTED,
@@ -1428,6 +1496,22 @@ static int bwd_entry(
       launch_dkv_band<T, TD, 1>(dka, bd, B, st);
       return ba_launch_status();
     });
+  }
+  if (blk) {
+    // the default plan's kernels in their block form (attn_bwd_blk.hip), after
+    // the pre-pass of both sides; every refusal comes before it
+    const ba_seg_verdict sv = ba_seg_bwd_support(kn);
+    if (sv.knob)
+      return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                     "%s=%d does not support a block mask (default backward "
+                     "plan only)",
+                     sv.knob, sv.value);
+    if ((D != 64 && D != 128) || (dtype != BAHIP_F16 && dtype != BAHIP_BF16))
+      return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                     "block mask: unsupported head_dim %d / dtype %d", (int)D,
+                     dtype);
+    if (int rc = ba_blk_check(*blk, B, Nk, Sq, Sk)) return rc;
+    return ba_blk_bwd(dqa, dva, dka, *blk, B, D, dtype, (hipStream_t)stream);
   }
   if (softcap > 0.f) {
     // the default plan's kernels in their soft-capped form
@@ -1534,6 +1618,27 @@ extern "C" int bahip_attn_bwd_softcap(
   return bwd_entry(dout, q, k, v, delta, lse, dq, dk, dv, B, Sq, Sk, N, Nk, D,
                    gs, qs, ks, vs, ds, ls, dqs, dks, dvs, scale, causal,
                    deterministic, dtype, stream, nullptr, nullptr, softcap);
+}
+
+extern "C" int bahip_attn_bwd_blk(
+    const void* dout, const void* q, const void* k, const void* v,
+    const float* delta, const float* lse, float* dq, float* dk, float* dv,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t gs[3], const int64_t qs[3], const int64_t ks[3],
+    const int64_t vs[3], const int64_t ds[2], const int64_t ls[2],
+    const int64_t dqs[3], const int64_t dks[3], const int64_t dvs[3],
+    float scale, int causal, int deterministic, int dtype,
+    const uint8_t* block_mask, const int64_t mask_strides[4], int64_t Bm,
+    int64_t Hm, int log2_block_size, void* blk_workspace,
+    int64_t blk_workspace_bytes, void* stream) {
+  const ba_blk_call bc = {block_mask,
+                          {mask_strides[0], mask_strides[1], mask_strides[2],
+                           mask_strides[3]},
+                          Bm, Hm, log2_block_size, blk_workspace,
+                          blk_workspace_bytes};
+  return bwd_entry(dout, q, k, v, delta, lse, dq, dk, dv, B, Sq, Sk, N, Nk, D,
+                   gs, qs, ks, vs, ds, ls, dqs, dks, dvs, scale, causal,
+                   deterministic, dtype, stream, nullptr, nullptr, 0.f, &bc);
 }
 
 // the equal-heads symbol: Nk = N

@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "band_support.h"
+#include "blk_support.h"
 #include "cap_support.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
@@ -190,6 +191,43 @@ __device__ __forceinline__ ba_cap_args ba_cap_of(const ba_cap_args& c) {
 // to far below the 16-bit rounding of P.
 __device__ __forceinline__ float ba_cap_tanh(float s, float a) {
   return __builtin_fmaf(-2.f, __builtin_amdgcn_rcpf(1.f + ba_exp2(s * a)), 1.f);
+}
+
+// ---- block masks (block-sparse attention) --------------------------------
+// The block form of a kernel takes one ba_blk_args in the same trailing pack:
+// the workgroup's tile loop runs over a LIST of streamed tiles instead of a
+// range (blk_support.h; written by ba_blk_prepass, attn_fwd_blk.hip), each
+// entry naming the waves that compute the tile.  A listed tile is wholly
+// block-visible to those waves, so the only element masks are the plain
+// kernel's own (range tail, causal).  So a pack holds nothing (plain), or one
+// of ba_seg_args, ba_band_args, ba_cap_args, ba_blk_args.
+struct ba_blk_args {
+  const uint32_t* list;  // [Bm][Hm][gridDim.x][stride] entries
+  const int32_t* cnt;    // [Bm][Hm][gridDim.x] entries of each list
+  int stride;            // capacity of one list: tiles of the streamed side
+  int Hm;                // mask heads
+  int b_mul, h_mul;      // 1 where the mask has the call's batch / KV heads,
+                         // 0 where its extent is 1
+};
+__device__ __forceinline__ ba_blk_args ba_blk_of(const ba_blk_args& a) {
+  return a;
+}
+// Word i of a pre-pass output, through the scalar data path: the workspace is
+// written by an earlier kernel of the stream and only read here, so it may be
+// addressed as constant memory, and a workgroup-uniform index then makes the
+// read an s_load_dword on lgkmcnt.  Through the generic pointer the compiler
+// cannot rule out the kernel's own stores and emits a per-lane global_load
+// whose vmcnt(0) wait also drains the tile prefetch issued just before it.
+template <typename W>
+__device__ __forceinline__ W ba_blk_word(const W* p, int64_t i) {
+  typedef const __attribute__((address_space(4))) W* cptr;
+  return ((cptr)(uintptr_t)p)[i];
+}
+// index of the list of (batch b, KV head nkv, own block blockIdx.x)
+__device__ __forceinline__ int64_t ba_blk_list_index(const ba_blk_args& a,
+                                                     int b, int nkv) {
+  return ((int64_t)(b * a.b_mul) * a.Hm + nkv * a.h_mul) * gridDim.x +
+         blockIdx.x;
 }
 
 // min and max of x over the wave, as wave-uniform (scalar) values

@@ -112,7 +112,14 @@ __device__ __forceinline__ int ba_buf_of(ba_dyn d) { return d.value; }
 // p = exp2(t * c2cap - m2).  A masked entry is masked on t, not on the raw
 // score: tanh of the raw mask level is -1, a finite score of -softcap that
 // would leak.  Same state contract (capped scores are bounded by c2cap, the
-// empty level stays BA_NEG_BIG).  Default variant with VSRC=0 only.
+// empty level stays BA_NEG_BIG).  Default variant with VSRC=0 only.  One
+// ba_blk_args = the block form (attn_common.h, blk_support.h): an indexed tile
+// stream.  The loop variable is a position in the workgroup's list and the
+// tile index comes from the entry; the pipeline stages list[t + 1] while
+// list[t] computes; a wave computes a tile iff the entry's bit says so; such a
+// tile is `full` by the plain rule and masked by the plain rule; no exp sees a
+// masked entry at the empty level, so there is no select.
+// Default variant with VSRC=0 only.
 template <typename T, int D, int KVBLK, int OUT_STATE, int VPATH, int SUBT,
           int NT = 512, int NBUF = 2, int KREG = 0, int VSRC = 0,
           typename... SEG>
@@ -133,10 +140,17 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
   using frag = typename MT::frag;
   constexpr bool HAS_BAND = ba_pack_is<ba_band_args, SEG...>;
   constexpr bool HAS_CAP = ba_pack_is<ba_cap_args, SEG...>;
-  constexpr bool HAS_SEG = sizeof...(SEG) != 0 && !HAS_BAND && !HAS_CAP;
+  constexpr bool HAS_BLK = ba_pack_is<ba_blk_args, SEG...>;
+  constexpr bool HAS_SEG =
+      sizeof...(SEG) != 0 && !HAS_BAND && !HAS_CAP && !HAS_BLK;
   // either form: entries can be masked inside the tensors' ranges, so a row
   // may see no key (weight-0 select, l = 0 epilogue)
   constexpr bool HAS_MASK = HAS_SEG || HAS_BAND;
+  static_assert(!HAS_BLK || (VPATH == 0 && SUBT == 1 && NT == 512 &&
+                             NBUF == 2 && KREG == 0 && VSRC == 0 &&
+                             KVBLK == BA_BLK_TILE && NT / 2 == BA_BLK_BLOCK),
+                "block masks: the default variant, V transposed in-kernel, "
+                "the tile sizes of blk_support.h");
   static_assert(!HAS_CAP || (VPATH == 0 && SUBT == 1 && NT == 512 &&
                              NBUF == 2 && KREG == 0 && VSRC == 0),
                 "soft-capping: the default variant, V transposed in-kernel");
@@ -297,8 +311,47 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
       return;
     }
   }
-  const int t_first = HAS_MASK ? trange.x : 0;
-  const int nt = HAS_MASK ? trange.y : nt_shape;
+  // block form: the tile loop runs over the workgroup's list, t is a position
+  // in it; e_cur is the entry of the tile being computed, e_nxt the one after
+  // it (read one entry ahead through ba_blk_word: a scalar load, so no vector
+  // wait stands between a tile's prefetch and its MFMAs)
+  const uint32_t* blst = nullptr;
+  uint32_t e_cur = 0, e_nxt = 0;
+  int wave_u = 0;
+  if constexpr (HAS_BLK) {
+    const ba_blk_args ba = ba_blk_of(seg...);
+    const int64_t li = ba_blk_list_index(ba, b, nkv);
+    trange.x = 0;
+    trange.y = ba_blk_word(ba.cnt, li);
+    if (trange.y <= 0) {
+      // an empty list (workgroup-uniform, no barrier yet): what the segment
+      // form writes
+      if (q_row < Sq && !(OUT_STATE && carry_in)) {
+        float* row = OUT_STATE
+                         ? st_acc + b * a_sb + (int64_t)q_row * a_ss + n * a_sh
+                         : o + (((int64_t)b * Sq + q_row) * N + n) * D;
+#pragma unroll
+        for (int dt = 0; dt < D / 32; ++dt)
+#pragma unroll
+          for (int r2 = 0; r2 < 16; ++r2) row[dt * 32 + ba_crow(r2, hi)] = 0.f;
+        if (hi == 0) {
+          if (OUT_STATE) {
+            st_m[b * ml_sb + n * ml_sh + q_row] = BA_NEG_BIG;
+            st_l[b * ml_sb + n * ml_sh + q_row] = 0.f;
+          } else {
+            lse[((int64_t)b * N + n) * Sq + q_row] = -__builtin_inff();
+          }
+        }
+      }
+      return;
+    }
+    blst = ba.list + li * ba.stride;
+    e_cur = ba_blk_word(blst, 0);
+    e_nxt = ba_blk_word(blst, min(1, trange.y - 1));
+    wave_u = __builtin_amdgcn_readfirstlane(wave);
+  }
+  const int t_first = (HAS_MASK || HAS_BLK) ? trange.x : 0;
+  const int nt = (HAS_MASK || HAS_BLK) ? trange.y : nt_shape;
   // cap form: the two constants, and whether the current tile was masked
   ba_cap_args cp = {0.f, 0.f};
   bool cap_masked = false;
@@ -648,7 +701,8 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
   frag kfr[KREG == 1 ? 2 : 1][D / 16];  // KREG: resident K fragments
   {  // prologue: tiles 0..NBUF-2
     u32x4_t kreg[PT], vreg[PT];
-    issue_loads(t_first, kreg, vreg);
+    issue_loads(HAS_BLK ? (int)(e_cur & BA_BLK_TILE_MASK) : t_first, kreg,
+                vreg);
     write_lds(0, kreg, vreg);
     if (KREG == 1) {
       load_k_sub(0, 0, kfr[0]);
@@ -675,13 +729,22 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
   // v_or per access — ~40 issue slots per tile in an issue-bound loop
   auto tile_body = [&](int t, auto curc) {
     const int cur = ba_buf_of(curc);  // compile-time literal for ba_ic
-    const int kv0 = t * KVBLK;
+    // block form: tile list[t] computes while tile list[t + 1] is staged
+    const int kv0 = (HAS_BLK ? (int)(e_cur & BA_BLK_TILE_MASK) : t) * KVBLK;
     const bool has_next = (t + AHEAD) < nt;
     u32x4_t kreg[PT], vreg[PT];
-    if (has_next) issue_loads(t + AHEAD, kreg, vreg);
+    if (has_next)
+      issue_loads(HAS_BLK ? (int)(e_nxt & BA_BLK_TILE_MASK) : t + AHEAD, kreg,
+                  vreg);
 
     bool active, full;
-    if constexpr (HAS_SEG) {
+    if constexpr (HAS_BLK) {
+      // a wave whose bit is clear skips the tile's MFMAs and still meets the
+      // barrier; the pre-pass folded the causal tile test into the bit
+      active = (e_cur >> (BA_BLK_TILE_BITS + wave_u)) & 1;
+      e_cur = e_nxt;
+      e_nxt = ba_blk_word(blst, min(t + 2, nt - 1));
+    } else if constexpr (HAS_SEG) {
       // segment form: the tile's (min, max) ids against the wave's; a full
       // tile also has one id on both sides
       const int2 mm = tmm[t];
@@ -885,7 +948,8 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
     } else {
       // segment form: a row that saw no key has l = 0: o = 0, lse = -inf
       float inv_l = 1.f / lsum;
-      if constexpr (HAS_MASK) inv_l = lsum == 0.f ? 0.f : inv_l;
+      // (block form: a wave that no entry names)
+      if constexpr (HAS_MASK || HAS_BLK) inv_l = lsum == 0.f ? 0.f : inv_l;
       float* orow = o + (((int64_t)b * Sq + q_row) * N + n) * D;
 #pragma unroll
       for (int dt = 0; dt < D / 32; ++dt)
@@ -1372,7 +1436,7 @@ static int fwd_entry(void* hip_function, int out_state, const void* q,
                      int carry_in, void* ws, int64_t ws_bytes, void* stream,
                      const fwd_seg_call* seg = nullptr,
                      const fwd_band_call* band = nullptr,
-                     float softcap = 0.f) {
+                     float softcap = 0.f, const ba_blk_call* blk = nullptr) {
   if (causal && Sq != Sk)
     return ba_fail(BAHIP_ERR_CAUSAL_SHAPE,
                    "causal tiles require Sq == Sk (%d vs %d)", (int)Sq,
@@ -1394,6 +1458,7 @@ static int fwd_entry(void* hip_function, int out_state, const void* q,
     // only; the V^T workspace is ignored and BA_FWD_VT is not consulted
     const char* what = seg            ? "segment ids"
                        : band         ? "a band"
+                       : blk          ? "a block mask"
                        : hip_function ? "a module-launched forward"
                                       : nullptr;
     if (what)
@@ -1421,6 +1486,19 @@ static int fwd_entry(void* hip_function, int out_state, const void* q,
   if (softcap > 0.f)
     return fwd_cap_entry(a, softcap, out_state, B, Sq, Sk, D, dtype,
                          (hipStream_t)stream);
+  if (blk) {
+    // The forward with a block mask: as with ids and bands, the default
+    // variant only, V transposed in the kernel (the V^T workspace is
+    // ignored), never the module kernel.  Every refusal comes before the
+    // pre-pass, so a refused call launches nothing.
+    if (int rc = fwd_default_variant_only("a block mask")) return rc;
+    if ((D != 64 && D != 128) || (dtype != BAHIP_F16 && dtype != BAHIP_BF16))
+      return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                     "block mask: unsupported head_dim %d / dtype %d", (int)D,
+                     dtype);
+    if (int rc = ba_blk_check(*blk, B, Nk, Sq, Sk)) return rc;
+    return ba_blk_fwd(a, *blk, out_state, B, D, dtype, (hipStream_t)stream);
+  }
   if (hip_function) {
     if (D != 128 || (dtype != BAHIP_F16 && dtype != BAHIP_BF16))
       return ba_fail(BAHIP_ERR_UNSUPPORTED,
@@ -1613,6 +1691,69 @@ extern "C" int bahip_attn_fwd_accum_softcap(
                    causal, dtype, acc, m, l, acc_strides, ml_strides, carry_in,
                    workspace, workspace_bytes, stream, nullptr, nullptr,
                    capped ? softcap : 0.f);
+}
+
+extern "C" int bahip_attn_fwd_blk(
+    const void* q, const void* k, const void* v, float* o, float* lse,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    const uint8_t* block_mask, const int64_t mask_strides[4], int64_t Bm,
+    int64_t Hm, int log2_block_size, void* blk_workspace,
+    int64_t blk_workspace_bytes, void* stream) {
+  const ba_blk_call bc = {block_mask,
+                          {mask_strides[0], mask_strides[1], mask_strides[2],
+                           mask_strides[3]},
+                          Bm, Hm, log2_block_size, blk_workspace,
+                          blk_workspace_bytes};
+  return fwd_entry(nullptr, 0, q, k, v, o, lse, B, Sq, Sk, N, Nk, D, q_strides,
+                   k_strides, v_strides, softmax_scale, causal, dtype, nullptr,
+                   nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, stream,
+                   nullptr, nullptr, 0.f, &bc);
+}
+
+extern "C" int bahip_attn_fwd_accum_blk(
+    void* hip_function, const void* q, const void* k, const void* v,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    float* acc, float* m, float* l, const int64_t acc_strides[3],
+    const int64_t ml_strides[2], int carry_in, const uint8_t* block_mask,
+    const int64_t mask_strides[4], int64_t Bm, int64_t Hm,
+    int log2_block_size, void* blk_workspace, int64_t blk_workspace_bytes,
+    void* stream) {
+  const ba_blk_call bc = {block_mask,
+                          {mask_strides[0], mask_strides[1], mask_strides[2],
+                           mask_strides[3]},
+                          Bm, Hm, log2_block_size, blk_workspace,
+                          blk_workspace_bytes};
+  return fwd_entry(hip_function, 1, q, k, v, nullptr, nullptr, B, Sq, Sk, N,
+                   Nk, D, q_strides, k_strides, v_strides, softmax_scale,
+                   causal, dtype, acc, m, l, acc_strides, ml_strides, carry_in,
+                   nullptr, 0, stream, nullptr, nullptr, 0.f, &bc);
+}
+
+extern "C" int64_t bahip_attn_blk_workspace_bytes(int64_t Bm, int64_t Hm,
+                                                  int64_t Sq, int64_t Sk) {
+  return ba_blk_ws_bytes(Bm, Hm, Sq, Sk);
+}
+
+extern "C" int bahip_attn_blk_prepass(
+    const uint8_t* block_mask, const int64_t mask_strides[4], int64_t Bm,
+    int64_t Hm, int log2_block_size, int64_t Sq, int64_t Sk, int causal,
+    void* blk_workspace, int64_t blk_workspace_bytes, void* stream) {
+  if (causal && Sq != Sk)
+    return ba_fail(BAHIP_ERR_CAUSAL_SHAPE,
+                   "causal tiles require Sq == Sk (%d vs %d)", (int)Sq,
+                   (int)Sk);
+  const ba_blk_call bc = {block_mask,
+                          {mask_strides[0], mask_strides[1], mask_strides[2],
+                           mask_strides[3]},
+                          Bm, Hm, log2_block_size, blk_workspace,
+                          blk_workspace_bytes};
+  // no call here to take B and Nk from: the mask's own extents pass
+  if (int rc = ba_blk_check(bc, Bm, Hm, Sq, Sk)) return rc;
+  return ba_blk_prepass(bc, Sq, Sk, causal, true, true, (hipStream_t)stream);
 }
 
 extern "C" int bahip_attn_fwd_state_init(

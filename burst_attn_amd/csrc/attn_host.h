@@ -9,6 +9,7 @@
 #include <stdlib.h>
 
 #include "../../include/burst_attn_hip.h"
+#include "blk_support.h"
 #include "cap_support.h"
 
 // One message buffer for both translation units (C++17 inline variable);
@@ -112,6 +113,59 @@ int ba_cap_fwd(const fwd_args& a, const ba_cap_args& cp, int out_state,
                int64_t B, int64_t D, int dtype, hipStream_t stream);
 int ba_cap_bwd(const bwd_dq_args& dq, const bwd_dq_args& dv,
                const bwd_dq_args& dk, const ba_cap_args& cp, int64_t B,
+               int64_t D, int dtype, hipStream_t stream);
+
+// Block form of the D = 64/128 kernels (blk_support.h): what a *_blk entry
+// point adds to the plain call, its validation, the pre-pass and the launches
+// of the default forward variant and the default backward plan's three
+// kernels (attn_fwd_blk.hip / attn_bwd_blk.hip, built without packed fp32 VALU
+// ops).  The callers have validated shapes, heads and knobs.
+struct ba_blk_call {
+  const uint8_t* mask;  // [Bm][Hm][ceil(Sq / BS)][ceil(Sk / BS)], nonzero = set
+  int64_t ms[4];        // its element strides
+  int64_t Bm, Hm;
+  int log2_bs;
+  void* ws;
+  int64_t ws_bytes;
+};
+inline int ba_blk_check(const ba_blk_call& c, int64_t B, int64_t Nk,
+                        int64_t Sq, int64_t Sk) {
+  if (!c.mask)
+    return ba_fail(BAHIP_ERR_BLOCK_MASK, "block mask: the mask is null");
+  if (!ba_blk_size_ok(c.log2_bs))
+    return ba_fail(BAHIP_ERR_BLOCK_MASK,
+                   "block mask: the block size must be a power of two >= 64 "
+                   "(its log2 was given as %d)",
+                   c.log2_bs);
+  if (c.Bm != 1 && c.Bm != B)
+    return ba_fail(BAHIP_ERR_BLOCK_MASK,
+                   "block mask: Bm=%d must be 1 or the batch size B=%d",
+                   (int)c.Bm, (int)B);
+  if (c.Hm != 1 && c.Hm != Nk)
+    return ba_fail(BAHIP_ERR_BLOCK_MASK,
+                   "block mask: Hm=%d must be 1 or the KV heads Nk=%d",
+                   (int)c.Hm, (int)Nk);
+  if (B < 1 || B > 65535 || Nk > 65535 || Sq < 1 || Sk < 1 ||
+      Sq > BA_BLK_MAX_S || Sk > BA_BLK_MAX_S)
+    return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                   "block mask: unsupported shape B=%d Sq=%lld Sk=%lld Nk=%d",
+                   (int)B, (long long)Sq, (long long)Sk, (int)Nk);
+  const int64_t need = ba_blk_ws_bytes(c.Bm, c.Hm, Sq, Sk);
+  if (!c.ws || c.ws_bytes < need)
+    return ba_fail(BAHIP_ERR_WORKSPACE,
+                   "block-mask workspace of %lld bytes is smaller than the "
+                   "%lld needed",
+                   (long long)(c.ws ? c.ws_bytes : 0), (long long)need);
+  return 0;
+}
+// the lists of the q-owning kernels (q_side), the kv-owning ones (kv_side),
+// or both, into c.ws
+int ba_blk_prepass(const ba_blk_call& c, int64_t Sq, int64_t Sk, int causal,
+                   bool q_side, bool kv_side, hipStream_t stream);
+int ba_blk_fwd(const fwd_args& a, const ba_blk_call& c, int out_state,
+               int64_t B, int64_t D, int dtype, hipStream_t stream);
+int ba_blk_bwd(const bwd_dq_args& dq, const bwd_dq_args& dv,
+               const bwd_dq_args& dk, const ba_blk_call& c, int64_t B,
                int64_t D, int dtype, hipStream_t stream);
 
 // f(ba_td<T, D>{}) for the supported (head_dim, dtype) pairs, else 1002.

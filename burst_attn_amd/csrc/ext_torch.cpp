@@ -148,6 +148,75 @@ bool softcap_given(double softcap, const SegIds& seg, bool band) {
   return true;
 }
 
+// The block mask of a call: a uint8 tensor [Bm, Hm, ceil(Sq/BS), ceil(Sk/BS)]
+// on q's device, any strides (they go to the kernel side as they are), with
+// the pre-pass workspace: the caller's (handed on with its true size, so that
+// whether it is large enough is the launcher's check) or one allocated per
+// call on the current stream.  Never together with ids, a band or a cap (those
+// combinations have no kernel form yet).  Bm, Hm and BS are the launcher's to
+// refuse.
+struct BlkMask {
+  const uint8_t* m = nullptr;
+  int64_t ms[4] = {0, 0, 0, 0}, Bm = 0, Hm = 0;
+  int log2_bs = -1;  // -1: not a power of two
+  at::Tensor ws;
+  void* ws_ptr() const { return ws.numel() ? ws.data_ptr() : nullptr; }
+  int64_t ws_bytes() const { return ws.numel() * ws.element_size(); }
+};
+
+BlkMask blk_mask(const c10::optional<at::Tensor>& mask, int64_t block_size,
+                 const c10::optional<at::Tensor>& blk_ws, const at::Tensor& q,
+                 int64_t Sq, int64_t Sk, const SegIds& seg, bool band,
+                 double softcap) {
+  BlkMask b;
+  if (!mask.has_value()) return b;
+  TORCH_CHECK(!seg.q, "block_mask and q_seg/kv_seg are not supported together "
+                      "yet");
+  TORCH_CHECK(!band, "block_mask and band_lo/band_hi are not supported "
+                     "together yet");
+  TORCH_CHECK(softcap == 0.0, "block_mask and softcap are not supported "
+                              "together yet");
+  const at::Tensor& m = *mask;
+  TORCH_CHECK(m.scalar_type() == at::kByte, "block_mask must be uint8, got ",
+              m.scalar_type());
+  TORCH_CHECK(m.device() == q.device(), "block_mask must be on q's device");
+  TORCH_CHECK(m.dim() == 4, "block_mask must be [Bm, Hm, q blocks, kv blocks]");
+  if (block_size > 0 && (block_size & (block_size - 1)) == 0) {
+    while ((int64_t(1) << (b.log2_bs + 1)) <= block_size) ++b.log2_bs;
+    TORCH_CHECK(m.size(2) == (Sq + block_size - 1) / block_size &&
+                    m.size(3) == (Sk + block_size - 1) / block_size,
+                "block_mask must be [Bm, Hm, ", (Sq + block_size - 1) / block_size,
+                ", ", (Sk + block_size - 1) / block_size, "] for block_size ",
+                block_size, ", got ", m.sizes());
+  }
+  b.m = m.data_ptr<uint8_t>();
+  for (int i = 0; i < 4; ++i) b.ms[i] = m.stride(i);
+  b.Bm = m.size(0);
+  b.Hm = m.size(1);
+  if (blk_ws.has_value()) {
+    TORCH_CHECK(blk_ws->device() == q.device() && blk_ws->is_contiguous(),
+                "blk_ws must be a contiguous tensor on q's device");
+    b.ws = *blk_ws;
+  } else {
+    b.ws = at::empty({bahip_attn_blk_workspace_bytes(b.Bm, b.Hm, Sq, Sk)},
+                     q.options().dtype(at::kByte));
+  }
+  return b;
+}
+
+// The block-mask pre-pass alone: the workspace as int32 words (layout:
+// bahip_attn_blk_prepass).  For tests and measurements.
+at::Tensor attn_blk_prepass(const at::Tensor& mask, int64_t block_size,
+                            int64_t Sq, int64_t Sk, bool causal) {
+  const BlkMask b = blk_mask(mask, block_size, c10::nullopt, mask, Sq, Sk,
+                             SegIds(), false, 0.0);
+  auto ws = b.ws.view(at::kInt);
+  BA_CALL(bahip_attn_blk_prepass(b.m, b.ms, b.Bm, b.Hm, b.log2_bs, Sq, Sk,
+                                 causal ? 1 : 0, b.ws_ptr(), b.ws_bytes(),
+                                 at::hip::getCurrentHIPStream().stream()));
+  return ws;
+}
+
 // The pre-pass alone on [B, Sq] / [B, Sk] ids: the workspace as int32
 // words (layout: bahip_attn_seg_prepass).  For tests and measurements.
 at::Tensor attn_seg_prepass(const at::Tensor& q_seg, const at::Tensor& kv_seg) {
@@ -176,15 +245,31 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k,
                                  const c10::optional<at::Tensor>& kv_seg,
                                  const c10::optional<int64_t>& band_lo,
                                  const c10::optional<int64_t>& band_hi,
-                                 double softcap) {
+                                 double softcap,
+                                 const c10::optional<at::Tensor>& block_mask,
+                                 int64_t block_size,
+                                 const c10::optional<at::Tensor>& blk_ws) {
   check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
   const SegIds seg = seg_ids(q_seg, kv_seg, q, k);
   const bool band = band_given(band_lo, band_hi, seg);
   const bool capped = softcap_given(softcap, seg, band);
+  const BlkMask blk = blk_mask(block_mask, block_size, blk_ws, q, Sq, Sk, seg,
+                               band, softcap);
   auto o = at::empty({B, Sq, N, D}, q.options().dtype(at::kFloat));
   auto lse = at::empty({B, N, Sq}, q.options().dtype(at::kFloat));
+  if (blk.m) {
+    // the block-sparse forward transposes V in the kernel: no image workspace
+    BA_CALL(bahip_attn_fwd_blk(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr<float>(),
+        lse.data_ptr<float>(), B, Sq, Sk, N, k.size(2), D, Strides3(q),
+        Strides3(k), Strides3(v), (float)softmax_scale, causal ? 1 : 0,
+        dtype_code(q), blk.m, blk.ms, blk.Bm, blk.Hm, blk.log2_bs,
+        blk.ws_ptr(), blk.ws_bytes(),
+        at::hip::getCurrentHIPStream().stream()));
+    return {o, lse};
+  }
   if (capped) {
     // the soft-capped forward transposes V in the kernel: no image workspace
     BA_CALL(bahip_attn_fwd_softcap(
@@ -258,7 +343,10 @@ void fwd_accum_call(void* asm_fn, const at::Tensor& q, const at::Tensor& k,
                     const c10::optional<at::Tensor>& kv_seg = c10::nullopt,
                     const c10::optional<int64_t>& band_lo = c10::nullopt,
                     const c10::optional<int64_t>& band_hi = c10::nullopt,
-                    double softcap = 0.0) {
+                    double softcap = 0.0,
+                    const c10::optional<at::Tensor>& block_mask = c10::nullopt,
+                    int64_t block_size = 64,
+                    const c10::optional<at::Tensor>& blk_ws = c10::nullopt) {
   check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
@@ -273,6 +361,19 @@ void fwd_accum_call(void* asm_fn, const at::Tensor& q, const at::Tensor& k,
   TORCH_CHECK(l.stride(0) == mls[0] && l.stride(1) == mls[1],
               "m/l stride mismatch");
   const bool band = band_given(band_lo, band_hi, seg);
+  const BlkMask blk = blk_mask(block_mask, block_size, blk_ws, q, Sq, Sk, seg,
+                               band, softcap);
+  if (blk.m) {
+    BA_CALL(bahip_attn_fwd_accum_blk(
+        nullptr, q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Sq, Sk, N,
+        k.size(2), D, Strides3(q), Strides3(k), Strides3(v),
+        (float)softmax_scale, causal ? 1 : 0, dtype_code(q),
+        acc.data_ptr<float>(), m.data_ptr<float>(), l.data_ptr<float>(),
+        Strides3(acc), mls, carry_in ? 1 : 0, blk.m, blk.ms, blk.Bm, blk.Hm,
+        blk.log2_bs, blk.ws_ptr(), blk.ws_bytes(),
+        at::hip::getCurrentHIPStream().stream()));
+    return;
+  }
   if (softcap_given(softcap, seg, band)) {
     BA_CALL(bahip_attn_fwd_accum_softcap(
         nullptr, q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Sq, Sk, N,
@@ -313,9 +414,13 @@ void attn_fwd_accum(const at::Tensor& q, const at::Tensor& k,
                     bool carry_in, const c10::optional<at::Tensor>& q_seg,
                     const c10::optional<at::Tensor>& kv_seg,
                     const c10::optional<int64_t>& band_lo,
-                    const c10::optional<int64_t>& band_hi, double softcap) {
+                    const c10::optional<int64_t>& band_hi, double softcap,
+                    const c10::optional<at::Tensor>& block_mask,
+                    int64_t block_size,
+                    const c10::optional<at::Tensor>& blk_ws) {
   fwd_accum_call(nullptr, q, k, v, softmax_scale, causal, acc, m, l, carry_in,
-                 q_seg, kv_seg, band_lo, band_hi, softcap);
+                 q_seg, kv_seg, band_lo, band_hi, softcap, block_mask,
+                 block_size, blk_ws);
 }
 
 // The empty carry-in state ("no key seen yet") written into acc [B,S,N,D],
@@ -399,7 +504,10 @@ void attn_bwd_accum(const at::Tensor& dout, const at::Tensor& q,
                     const c10::optional<at::Tensor>& q_seg,
                     const c10::optional<at::Tensor>& kv_seg,
                     const c10::optional<int64_t>& band_lo,
-                    const c10::optional<int64_t>& band_hi, double softcap) {
+                    const c10::optional<int64_t>& band_hi, double softcap,
+                    const c10::optional<at::Tensor>& block_mask,
+                    int64_t block_size,
+                    const c10::optional<at::Tensor>& blk_ws) {
   check_qkv(dout, "dout");
   check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
@@ -423,6 +531,19 @@ void attn_bwd_accum(const at::Tensor& dout, const at::Tensor& q,
   int64_t ls[2] = {lse.stride(0), lse.stride(1)};
   auto stream = at::hip::getCurrentHIPStream().stream();
   const bool band = band_given(band_lo, band_hi, seg);
+  const BlkMask blk = blk_mask(block_mask, block_size, blk_ws, q, Sq, Sk, seg,
+                               band, softcap);
+  if (blk.m) {
+    BA_CALL(bahip_attn_bwd_blk(
+        dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+        delta.data_ptr<float>(), lse.data_ptr<float>(), dq.data_ptr<float>(),
+        dk.data_ptr<float>(), dv.data_ptr<float>(), B, Sq, Sk, N, k.size(2), D,
+        Strides3(dout), Strides3(q), Strides3(k), Strides3(v), ds, ls,
+        Strides3(dq), Strides3(dk), Strides3(dv), (float)softmax_scale,
+        causal ? 1 : 0, deterministic ? 1 : 0, dtype_code(q), blk.m, blk.ms,
+        blk.Bm, blk.Hm, blk.log2_bs, blk.ws_ptr(), blk.ws_bytes(), stream));
+    return;
+  }
   if (softcap_given(softcap, seg, band)) {
     BA_CALL(bahip_attn_bwd_softcap(
         dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
@@ -464,7 +585,10 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
                                  const c10::optional<at::Tensor>& kv_seg,
                                  const c10::optional<int64_t>& band_lo,
                                  const c10::optional<int64_t>& band_hi,
-                                 double softcap) {
+                                 double softcap,
+                                 const c10::optional<at::Tensor>& block_mask,
+                                 int64_t block_size,
+                                 const c10::optional<at::Tensor>& blk_ws) {
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
   // zero-filled: the kernels accumulate, so this equals fresh outputs
@@ -475,7 +599,7 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
   auto dv = at::zeros({B, Sk, Nk, D}, q.options().dtype(at::kFloat));
   attn_bwd_accum(dout, q, k, v, delta, lse, softmax_scale, causal,
                  deterministic, dq, dk, dv, q_seg, kv_seg, band_lo, band_hi,
-                 softcap);
+                 softcap, block_mask, block_size, blk_ws);
   return {dq, dk, dv};
 }
 
@@ -542,14 +666,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("softmax_scale"),
         py::arg("causal"), py::arg("q_seg") = py::none(),
         py::arg("kv_seg") = py::none(), py::arg("band_lo") = py::none(),
-        py::arg("band_hi") = py::none(), py::arg("softcap") = 0.0);
+        py::arg("band_hi") = py::none(), py::arg("softcap") = 0.0,
+        py::arg("block_mask") = py::none(), py::arg("block_size") = 64,
+        py::arg("blk_ws") = py::none());
   m.def("attn_fwd_accum", &attn_fwd_accum,
         "carry-in accumulator fwd tile (in-kernel LSE merge)", py::arg("q"),
         py::arg("k"), py::arg("v"), py::arg("softmax_scale"),
         py::arg("causal"), py::arg("acc"), py::arg("m"), py::arg("l"),
         py::arg("carry_in"), py::arg("q_seg") = py::none(),
         py::arg("kv_seg") = py::none(), py::arg("band_lo") = py::none(),
-        py::arg("band_hi") = py::none(), py::arg("softcap") = 0.0);
+        py::arg("band_hi") = py::none(), py::arg("softcap") = 0.0,
+        py::arg("block_mask") = py::none(), py::arg("block_size") = 64,
+        py::arg("blk_ws") = py::none());
   m.def("attn_fwd_state_init", &attn_fwd_state_init,
         "write the empty carry-in state (no key seen yet) into acc, m, l");
   m.def("attn_seg_prepass", &attn_seg_prepass,
@@ -557,6 +685,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "block ranges of both side pairs)");
   m.def("attn_seg_workspace_bytes", &bahip_attn_seg_workspace_bytes,
         "bytes of the segment-id pre-pass workspace of a (B, Sq, Sk) call");
+  m.def("attn_blk_prepass", &attn_blk_prepass,
+        "block-mask pre-pass alone: the int32 workspace (counts and tile lists "
+        "of both sides)",
+        py::arg("block_mask"), py::arg("block_size"), py::arg("Sq"),
+        py::arg("Sk"), py::arg("causal"));
+  m.def("attn_blk_workspace_bytes", &bahip_attn_blk_workspace_bytes,
+        "bytes of the block-mask pre-pass workspace of a (Bm, Hm, Sq, Sk) call");
   m.def("attn_fwd_finalize", &attn_fwd_finalize,
         "o = acc/l (cast), lse from state");
   m.def("attn_vt_image", &attn_vt_image,
@@ -573,7 +708,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("causal"), py::arg("deterministic"),
         py::arg("q_seg") = py::none(), py::arg("kv_seg") = py::none(),
         py::arg("band_lo") = py::none(), py::arg("band_hi") = py::none(),
-        py::arg("softcap") = 0.0);
+        py::arg("softcap") = 0.0,
+        py::arg("block_mask") = py::none(), py::arg("block_size") = 64,
+        py::arg("blk_ws") = py::none());
   m.def("attn_bwd_accum", &attn_bwd_accum,
         "bwd tile accumulating into fp32 dq/dk/dv views", py::arg("dout"),
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("delta"),
@@ -581,7 +718,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("deterministic"), py::arg("dq"), py::arg("dk"), py::arg("dv"),
         py::arg("q_seg") = py::none(), py::arg("kv_seg") = py::none(),
         py::arg("band_lo") = py::none(), py::arg("band_hi") = py::none(),
-        py::arg("softcap") = 0.0);
+        py::arg("softcap") = 0.0,
+        py::arg("block_mask") = py::none(), py::arg("block_size") = 64,
+        py::arg("blk_ws") = py::none());
   m.def("mfma_probe", &mfma_probe, "32x32x16 MFMA layout probe");
   m.def("tr16_probe", &tr16_probe, "ds_read_tr16_b64 semantics probe");
   m.def("attn_fwd_asm_load", &attn_fwd_asm_load,

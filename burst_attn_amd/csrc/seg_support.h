@@ -11,6 +11,7 @@
 #include "fwd_variants.h"
 
 // nullptr knob = supported; else the env name and value that rule ids out
+// (the band, cap and block forms ask the same two functions)
 struct ba_seg_verdict {
   const char* knob;
   int value;

@@ -58,6 +58,24 @@ knows: nothing new travels the ring, and each round hands the tile provider
 Without a cap the provider calls carry no such keyword.  A cap together with
 ``segment_ids`` or an effective window is refused.
 
+Block-sparse attention: the trailing keywords ``block_mask`` and
+``block_size`` of ``burst_attn_func`` (``torch.bool`` or ``uint8``
+``[Bm, Hm, s_local / BS, S_global / BS]``, ``Bm`` 1 or B, ``Hm`` 1 or Nk, BS a
+power of two >= 64).  Row ``qb`` is this rank's local query block ``qb`` in
+the layout the function already uses (zigzag with ``causal``, contiguous
+without), column ``kb`` the GLOBAL key block ``kb``; pair (i, j) is visible
+iff its block is set and, with ``causal``, ``j <= i`` on global positions.
+The rank's slab stays where q stays: in the forward the origin rank of the
+visiting k/v names the slab's columns of each (q piece, kv piece) pair
+(``block_tiles``) and the round is one ``fwd_accum(blocks=(sub-view, BS))``
+per pair into a state that starts empty; a sub-view without a set block
+launches nothing.  In the backward the slab travels with {delta-or-o,
+grad_output, q, lse} and the kv-resident rank selects its own columns.  The
+sub-views are views: nothing is copied per round.  Without a mask neither the
+payloads nor the provider calls change.  A mask together with
+``segment_ids``, an effective window, a cap, head_dim 256 or the striped op
+is refused.
+
 The two causal load-balancing layouts (see oracle/partition.py) run the
 same code: ``OpBurstAttn`` (zigzag: rank r holds global chunks [r] and
 [2W-1-r]) and ``OpBurstAttnStrip`` (striped: token t on rank t mod W) only
@@ -80,7 +98,7 @@ from .tile import get_tile_provider
 _logger = get_logger(__name__, level="WARN")
 
 __all__ = ["burst_attn_func", "burst_attn_func_striped", "OpBurstAttn",
-           "OpBurstAttnStrip", "window_tiles"]
+           "OpBurstAttnStrip", "window_tiles", "block_tiles"]
 
 
 def get_partition_id(double_group, r, process_group=None):
@@ -203,6 +221,33 @@ def window_tiles(layout, a, b, W, s_local, causal, window):
             else:
                 out.append((q_rows, kv_rows, (lo2, hi2), False))
     return out
+
+
+def block_tiles(a, b, W, s_local, causal):
+    """The sub-tiles that one ring round computes of the q chunk owned by
+    rank ``a`` against the kv chunk owned by rank ``b`` under a block mask: a
+    list of ``(q_rows, kv_rows, kv_global_start, tile_causal)``, one per (q
+    piece, kv piece) pair of the two ranks (``_pieces``: two zigzag halves
+    each with ``causal``, one contiguous chunk without).  With ``causal`` a
+    pair wholly above the diagonal is dropped, the pair on it is a causal
+    call and a pair below it a plain one: the decisions of ``tile_window``.
+    ``kv_global_start`` locates the kv piece's columns in the mask."""
+    layout = "zigzag" if causal else "contiguous"
+    out = []
+    for lq, nq, Pq, _ in _pieces(layout, a, W, s_local):
+        for lk, nk, Pk, _ in _pieces(layout, b, W, s_local):
+            if causal and Pk > Pq:
+                continue
+            out.append((slice(lq, lq + nq), slice(lk, lk + nk), Pk,
+                        causal and Pk == Pq))
+    return out
+
+
+def _block_view(slab, bs, q_rows, kv_rows, kv_start):
+    """The slab's blocks of local q rows ``q_rows`` against the kv piece
+    ``kv_rows`` whose global positions start at ``kv_start``: a view."""
+    return slab[:, :, q_rows.start // bs:q_rows.stop // bs,
+                kv_start // bs:(kv_start + kv_rows.stop - kv_rows.start) // bs]
 
 
 def _window_layout(layout, causal):
@@ -354,10 +399,71 @@ def _check_softcap(softcap, segment_ids, window):
     return float(softcap)
 
 
-def _op_args(ids, window, softcap):
-    """The trailing arguments of the two ops: the ids always, the window and
-    the cap only when given, so that a call without them applies the op with
-    the argument list it had before they existed."""
+def _check_block_mask(block_mask, block_size, q, k, causal, segment_ids,
+                      window, softcap):
+    """None, or ``(slab, BS)``: this rank's mask as contiguous uint8
+    (converted once, here).  Everything that can be said without the world
+    size is checked here, before the op; the column count is the op's."""
+    if block_mask is None:
+        return None
+    bs = block_size
+    if (isinstance(bs, bool) or not isinstance(bs, int) or bs < 64
+            or bs & (bs - 1)):
+        raise ValueError(
+            f"block_size must be a power of two >= 64, got {bs!r} "
+            "(with block_mask)"
+        )
+    other = ("segment_ids" if segment_ids is not None
+             else "window_size" if window is not None
+             else "softcap" if softcap > 0 else None)
+    if other:
+        raise ValueError(
+            f"block_mask and {other} are not supported together yet"
+        )
+    if q.shape[3] == 256:
+        raise ValueError(
+            "head_dim 256 with block_mask is not supported yet: the "
+            "block-sparse tile kernels exist for head_dim 64 and 128 only"
+        )
+    if not isinstance(block_mask, torch.Tensor):
+        raise ValueError(
+            f"block_mask must be a tensor, got {type(block_mask).__name__}"
+        )
+    if block_mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(
+            f"block_mask must be torch.bool or uint8, got {block_mask.dtype}"
+        )
+    if block_mask.device != q.device:
+        raise ValueError(
+            f"block_mask is on {block_mask.device}, q on {q.device}"
+        )
+    s_local, unit = q.shape[1], (2 * bs if causal else bs)
+    if s_local % unit:
+        raise ValueError(
+            f"block_mask: the per-rank seqlen {s_local} must be a multiple of "
+            f"{'2 * ' if causal else ''}block_size = {unit}"
+            + (" (causal: both zigzag pieces start on block boundaries)"
+               if causal else "")
+        )
+    rows = s_local // bs
+    shape = tuple(block_mask.shape)
+    if (len(shape) != 4 or shape[0] not in (1, q.shape[0])
+            or shape[1] not in (1, k.shape[2]) or shape[2] != rows
+            or shape[3] < rows or shape[3] % rows):
+        raise ValueError(
+            "block_mask must be [1 or B, 1 or Nk, s_local / block_size, "
+            f"S_global / block_size] = [1|{q.shape[0]}, 1|{k.shape[2]}, "
+            f"{rows}, {rows} * world size], got {shape}"
+        )
+    return block_mask.to(torch.uint8).contiguous(), bs
+
+
+def _op_args(ids, window, softcap, blocks=None):
+    """The trailing arguments of the two ops: the ids always, the window, the
+    cap and the block mask only when given, so that a call without them
+    applies the op with the argument list it had before they existed."""
+    if blocks is not None:
+        return (ids, None, 0.0, *blocks)  # never with ids, a window or a cap
     if softcap > 0:
         return (ids, None, softcap)  # never with a window
     return (ids,) if window is None else (ids, window)
@@ -378,15 +484,19 @@ def burst_attn_func(
     segment_ids: torch.Tensor = None,
     window_size=None,
     softcap: float = 0.0,
+    block_mask: torch.Tensor = None,
+    block_size: int = 64,
 ):
     _check_heads(q, k, v)
     window = _check_window(window_size, causal, segment_ids)
     _check_masks_for_head_dim(q, segment_ids, window)
     softcap = _check_softcap(softcap, segment_ids, window)
+    blocks = _check_block_mask(block_mask, block_size, q, k, causal,
+                               segment_ids, window, softcap)
     return OpBurstAttn.apply(
         q, k, v, softmax_scale, flash, causal, optimize_bwd_comm,
         deterministic, process_group, double_group,
-        *_op_args(_check_segment_ids(segment_ids, q), window, softcap),
+        *_op_args(_check_segment_ids(segment_ids, q), window, softcap, blocks),
     )
 
 
@@ -405,8 +515,16 @@ def burst_attn_func_striped(
     segment_ids: torch.Tensor = None,
     window_size=None,
     softcap: float = 0.0,
+    block_mask: torch.Tensor = None,
+    block_size: int = 64,
 ):
     _check_heads(q, k, v)
+    if block_mask is not None:
+        raise ValueError(
+            "burst_attn_func_striped does not support block_mask / "
+            "block_size: a global key block is not a run of local rows in "
+            "the striped layout; use burst_attn_func"
+        )
     window = _check_window(window_size, causal, segment_ids)
     _check_masks_for_head_dim(q, segment_ids, window)
     softcap = _check_softcap(softcap, segment_ids, window)
@@ -420,13 +538,16 @@ def burst_attn_func_striped(
 def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
                   causal=False, optimize_bwd_comm=False, deterministic=False,
                   process_group=None, double_group=[None, None],
-                  segment_ids=None, window=None, softcap=0.0):
+                  segment_ids=None, window=None, softcap=0.0, block_mask=None,
+                  block_size=64):
     """Forward of both layouts: q stays, {k, v} travel the ring (with the
     kv ids, when there are segment ids).  With a window every round is the
-    sub-tiles of ``window_tiles``, merged into a state that starts empty.
+    sub-tiles of ``window_tiles``, merged into a state that starts empty; with
+    a block mask those of ``block_tiles``, each on its view of the rank's slab.
     With a cap every round's tile call carries it."""
     _check_flash_arg(flash)
     ctx.segment_ids = ids = segment_ids
+    ctx.blocks = None if block_mask is None else (block_mask, block_size)
     ctx.window = window
     ctx.softcap = softcap
     cap = {"softcap": softcap} if softcap > 0 else {}
@@ -458,11 +579,22 @@ def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
     if window is not None:
         state = P.fwd_empty_state(q)
         wlayout = _window_layout(layout, causal)
+    if block_mask is not None:
+        if block_mask.shape[3] != W * block_mask.shape[2]:
+            raise ValueError(
+                f"block_mask has {block_mask.shape[3]} key block columns, "
+                f"the {W} ranks' sequence has {W * block_mask.shape[2]} "
+                f"blocks of block_size {block_size}"
+            )
+        state = P.fwd_empty_state(q)
+        # one host copy answers "does this sub-view hold a set block" for
+        # every round without a device sync per round
+        slab_host = block_mask.cpu()
     record = []
     for r in range(1, W + 1):
         src = get_partition_id(double_group, r, process_group)
         record.append(src)
-        if window is None:
+        if window is None and block_mask is None:
             qw, kw, tile_causal = tile_window(layout, rank, src, causal, q.shape[1])
         payload = [k, v] if ids is None else [k, v, kv_ids]
         if r != W:
@@ -475,6 +607,16 @@ def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
                     state, q[:, qw], k[:, kw], v[:, kw], scale, tile_causal,
                     row_offset=qw.start,
                     **({} if band is None else {"band": band}))
+        elif block_mask is not None:
+            for qw, kw, kv0, tile_causal in block_tiles(
+                    rank, src, W, q.shape[1], causal):
+                if not _block_view(slab_host, block_size, qw, kw, kv0).any():
+                    continue  # no set block: nothing to launch
+                state = P.fwd_accum(
+                    state, q[:, qw], k[:, kw], v[:, kw], scale, tile_causal,
+                    row_offset=qw.start,
+                    blocks=(_block_view(block_mask, block_size, qw, kw, kv0),
+                            block_size))
         else:
             seg = {} if ids is None else {"seg": (ids[:, qw], kv_ids[:, kw])}
             state = P.fwd_accum(state, q[:, qw], k[:, kw], v[:, kw], scale,
@@ -536,6 +678,10 @@ def _ring_backward(layout, ctx, grad_output):
     # travels with q as the q side
     ids = ctx.segment_ids
     q_ids = None if ids is None else replicate(ids)
+    # the q side's slab of the block mask travels with q; this rank selects
+    # its own key-block columns of whichever slab is visiting
+    blocks = ctx.blocks
+    q_slab = None if blocks is None else replicate(blocks[0])
     window = ctx.window
     cap = {"softcap": ctx.softcap} if ctx.softcap > 0 else {}
     P = get_tile_provider()
@@ -568,13 +714,17 @@ def _ring_backward(layout, ctx, grad_output):
     read_bufs = [torch.empty_like(t) for t in (dlt, grad_output, q, lse)]
     if ids is not None:
         read_bufs.append(torch.empty_like(q_ids))
+    if blocks is not None:
+        read_bufs.append(torch.empty_like(q_slab))
     for r in range(1, W + 1):
         src = get_partition_id(double_group, r, group)
-        if window is None:
+        if window is None and blocks is None:
             qw, kw, tile_causal = tile_window(layout, src, rank, causal, q.shape[1])
         payload = [dlt, grad_output, q, lse]
         if ids is not None:
             payload.append(q_ids)
+        if blocks is not None:
+            payload.append(q_slab)
         if r != W:
             ring.double_ring_send_recv(payload, read_bufs, r)
             ring.commit()
@@ -599,6 +749,20 @@ def _ring_backward(layout, ctx, grad_output):
             # empty slice when the round computed nothing)
             qw = slice(min((t[0].start for t in tiles), default=0),
                        max((t[0].stop for t in tiles), default=0))
+        elif blocks is not None:
+            # (a sub-view without a set block is not tested for here: that
+            # would sync on the slab that just arrived; its kernels leave on
+            # their empty lists)
+            for qr, kr, kv0, tile_causal in block_tiles(
+                    src, rank, W, q.shape[1], causal):
+                P.bwd_accum(
+                    grad_output[:, qr], q[:, qr], k[:, kr], v[:, kr],
+                    delta[:, :, qr], lse[:, :, qr], scale, tile_causal,
+                    ctx.deterministic, tgt[:, qr], dk[:, kr], dv[:, kr],
+                    blocks=(_block_view(q_slab, blocks[1], qr, kr, kv0),
+                            blocks[1]),
+                )
+            qw = _ALL
         else:
             P.bwd_accum(
                 grad_output[:, qw], q[:, qw], k[:, kw], v[:, kw],
@@ -612,6 +776,8 @@ def _ring_backward(layout, ctx, grad_output):
             dlt, grad_output, q, lse = recv[:4]
             if ids is not None:
                 q_ids = recv[4]
+            if blocks is not None:
+                q_slab = recv[4]
         ring.wait()
         if r != 1:
             dq = dq_hop.finish(dq)
@@ -625,7 +791,8 @@ def _ring_backward(layout, ctx, grad_output):
         dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype),
         None, None, None, None, None, None, None, None,
         # one None per trailing argument of _op_args beyond the ids
-        *((None, None) if cap else () if window is None else (None,)),
+        *((None,) * 4 if blocks is not None else (None, None) if cap
+          else () if window is None else (None,)),
     )
 
 

@@ -74,6 +74,19 @@ of a ring passes the same value.  ``None`` (and ``0.0``, the flash-attn
 "off") is the call without it.  ``softcap`` with ``seg`` or ``band`` is
 refused.  A caller without a cap passes no ``softcap`` keyword at all.
 
+Block masks (block-sparse attention): the same four methods take an optional
+keyword ``blocks=(mask2d, BS)``: a ``uint8`` tensor
+``[Bm, Hm, ceil(Sq/BS), ceil(Sk/BS)]`` on q's device, any strides (a view is
+handed to the kernel side by its element strides, nothing is copied), and the
+block size, a power of two >= 64.  ``Bm`` is 1 or ``B``, ``Hm`` 1 or ``Nk``:
+one row of blocks per KV head, shared by the query heads of its group.  Pair
+(q row i, kv row j) *of the tensors passed* is then visible iff
+``mask2d[b, h // G, i // BS, j // BS]`` is nonzero, on top of ``causal``
+(which keeps demanding ``Sq == Sk``).  The kernels walk lists of the set
+blocks' tiles, so work follows the number of set blocks.  A row that sees no
+key behaves as with ids.  ``blocks`` with ``seg``, ``band`` or ``softcap`` is
+refused.  A caller without a mask passes no ``blocks`` keyword at all.
+
 The default provider is the gfx950 HIP extension and FAILS LOUDLY if the
 extension is missing on a GPU machine — there is no CPU/eager fallback in
 the product path.  Tests may inject an oracle-backed provider via
@@ -141,31 +154,49 @@ class HipTileProvider:
                 + " are not supported together yet")
         return {"softcap": float(softcap)}
 
-    def fwd(self, q, k, v, scale, causal, seg=None, band=None, softcap=None):
+    @staticmethod
+    def _blk_kw(blocks, seg, band, softcap):
+        """The extension's keywords of a ``blocks=(mask2d, BS)``; none
+        without."""
+        if blocks is None:
+            return {}
+        other = ("seg" if seg is not None else "band" if band is not None
+                 else "softcap" if softcap else None)
+        if other:
+            raise RuntimeError(
+                f"blocks and {other} are not supported together yet")
+        mask2d, bs = blocks
+        return {"block_mask": mask2d, "block_size": int(bs)}
+
+    def fwd(self, q, k, v, scale, causal, seg=None, band=None, softcap=None,
+            blocks=None):
         q_seg, kv_seg = seg if seg is not None else (None, None)
         return self._ext.attn_fwd(q, k, v, float(scale), bool(causal),
                                   q_seg, kv_seg, **self._band_kw(band),
-                                  **self._cap_kw(softcap, seg, band))
+                                  **self._cap_kw(softcap, seg, band),
+                                  **self._blk_kw(blocks, seg, band, softcap))
 
     def bwd_preprocess(self, o, do, out=None):
         return self._ext.attn_bwd_preprocess(o, do, out)
 
     def bwd(self, do, q, k, v, delta, lse, scale, causal, deterministic,
-            seg=None, band=None, softcap=None):
+            seg=None, band=None, softcap=None, blocks=None):
         q_seg, kv_seg = seg if seg is not None else (None, None)
         return self._ext.attn_bwd(
             do, q, k, v, delta, lse, float(scale), bool(causal),
             bool(deterministic), q_seg, kv_seg, **self._band_kw(band),
             **self._cap_kw(softcap, seg, band),
+            **self._blk_kw(blocks, seg, band, softcap),
         )
 
     def bwd_accum(self, do, q, k, v, delta, lse, scale, causal, deterministic,
-                  dq, dk, dv, seg=None, band=None, softcap=None):
+                  dq, dk, dv, seg=None, band=None, softcap=None, blocks=None):
         q_seg, kv_seg = seg if seg is not None else (None, None)
         self._ext.attn_bwd_accum(
             do, q, k, v, delta, lse, float(scale), bool(causal),
             bool(deterministic), dq, dk, dv, q_seg, kv_seg,
             **self._band_kw(band), **self._cap_kw(softcap, seg, band),
+            **self._blk_kw(blocks, seg, band, softcap),
         )
 
     def merge(self, o, lse, o_i, lse_i):
@@ -176,19 +207,21 @@ class HipTileProvider:
     # running max, l fp32 [B,N,S] running sum) over the rank's FULL chunk;
     # row_offset targets the zigzag-half / striped-shift row windows.
     def fwd_accum(self, state, q, k, v, scale, causal, row_offset=0, seg=None,
-                  band=None, softcap=None):
+                  band=None, softcap=None, blocks=None):
         cap_kw = self._cap_kw(softcap, seg, band)
+        blk_kw = self._blk_kw(blocks, seg, band, softcap)
         # the .s-built module carries the D=128 production variants only,
-        # and no segment, band or soft-capped form: with any of them the
-        # in-binary kernel runs
+        # and no segment, band, soft-capped or block form: with any of them
+        # the in-binary kernel runs
         if (self._asm_fwd and q.shape[3] == 128 and seg is None
-                and band is None and not cap_kw):
+                and band is None and not cap_kw and not blk_kw):
             accum = self._ext.attn_fwd_accum_asm
-        elif seg is not None or band is not None or cap_kw:
+        elif seg is not None or band is not None or cap_kw or blk_kw:
             q_seg, kv_seg = seg if seg is not None else (None, None)
             accum = functools.partial(self._ext.attn_fwd_accum,
                                       q_seg=q_seg, kv_seg=kv_seg,
-                                      **self._band_kw(band), **cap_kw)
+                                      **self._band_kw(band), **cap_kw,
+                                      **blk_kw)
         else:
             accum = self._ext.attn_fwd_accum
         if state is None:

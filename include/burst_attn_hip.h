@@ -128,6 +128,28 @@
  *     says (its V^T workspace argument is ignored) and never uses
  *     hip_function.  A cap together with segment ids or a band has no entry
  *     point.
+ *   - block masks (block-sparse attention): the *_blk entry points take,
+ *     before stream, a byte mask [Bm][Hm][ceil(Sq/BS)][ceil(Sk/BS)] with its
+ *     four element strides, its two leading extents, log2(BS) and a workspace
+ *     of bahip_attn_blk_workspace_bytes(Bm, Hm, Sq, Sk) bytes.  Pair (i, j) is
+ *     visible iff mask[b or 0][KV head of the q head, or 0][i / BS][j / BS] is
+ *     nonzero, on top of causal (which still demands Sq == Sk).  A pre-pass
+ *     on `stream` turns the mask into one list of 64-row tiles per 256-row
+ *     block of the side a kernel owns, and the kernels' tile loops run over
+ *     those lists: work follows the number of set blocks.  A q row whose
+ *     blocks are all clear gets o = 0, lse = -inf (stateless), an untouched
+ *     state (carry_in = 1) or an empty one (carry_in = 0), and adds nothing to
+ *     any gradient; a key nobody sees gets nothing added to dk / dv.  A null
+ *     mask, BS < 64 or not a power of two, Bm not in {1, B} or Hm not in
+ *     {1, Nk} returns BAHIP_ERR_BLOCK_MASK; a null or too small workspace
+ *     BAHIP_ERR_WORKSPACE; D = 256, another BA_FWD_* selection,
+ *     BA_BWD_FUSED=1/2, BA_BWD_DK_FLIP=1 or BA_DQ_PIPE=1
+ *     BAHIP_ERR_UNSUPPORTED naming what was asked.  Nothing is launched in
+ *     any of these cases.  D = 64 / 128, fp16 and bf16, GQA, strided slices;
+ *     the backward is as bitwise deterministic as the plain kernels.  The
+ *     forward transposes V in the kernel whatever BA_FWD_VT says and never
+ *     uses hip_function.  A block mask together with segment ids, a band or a
+ *     cap has no entry point.
  *   - stream is a hipStream_t.
  * Returns 0 on success; nonzero = error.  Every nonzero return sets the
  * calling thread's bahip_last_error() message and every success clears it.
@@ -160,6 +182,10 @@ extern "C" {
 #define BAHIP_ERR_BAND 1007           /* band_lo > band_hi */
 
 #define BAHIP_ERR_SOFTCAP 1008        /* softcap negative or not finite */
+
+#define BAHIP_ERR_BLOCK_MASK 1009     /* block mask null, BS < 64 or not a
+                                         power of two, Bm not in {1, B}, Hm
+                                         not in {1, Nk} */
 
 const char* bahip_last_error(void);
 
@@ -436,6 +462,58 @@ int bahip_attn_bwd_softcap(
     const int64_t dv_strides[3],
     float softmax_scale, int causal, int deterministic, int dtype,
     float softcap, void* stream);
+
+/* ---- block masks (see "block masks" above) --------------------------------
+ * bahip_attn_fwd_gqa, bahip_attn_fwd_accum_gqa and bahip_attn_bwd_gqa with a
+ * block mask.  The workspace holds, in 32-bit words, with L = Bm * Hm,
+ * nb(S) = ceil(S / 256) and nt(S) = ceil(S / 64):
+ *   q_cnt [L][nb(Sq)], q_list [L][nb(Sq)][nt(Sk)]   (forward, dq)
+ *   kv_cnt [L][nb(Sk)], kv_list [L][nb(Sk)][nt(Sq)] (dK, dV)
+ * a list's first cnt entries being (tile index | wave mask << 24), ascending.
+ * bahip_attn_blk_prepass writes both sides alone, for tests and measurements;
+ * the forward writes the q side, the backward both. */
+int64_t bahip_attn_blk_workspace_bytes(int64_t Bm, int64_t Hm, int64_t Sq,
+                                       int64_t Sk);
+int bahip_attn_blk_prepass(
+    const uint8_t* block_mask, const int64_t mask_strides[4], int64_t Bm,
+    int64_t Hm, int log2_block_size, int64_t Sq, int64_t Sk, int causal,
+    void* blk_workspace, int64_t blk_workspace_bytes, void* stream);
+int bahip_attn_fwd_blk(
+    const void* q, const void* k, const void* v,
+    float* o, float* lse,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3],
+    const int64_t k_strides[3],
+    const int64_t v_strides[3],
+    float softmax_scale, int causal, int dtype,
+    const uint8_t* block_mask, const int64_t mask_strides[4], int64_t Bm,
+    int64_t Hm, int log2_block_size, void* blk_workspace,
+    int64_t blk_workspace_bytes, void* stream);
+int bahip_attn_fwd_accum_blk(
+    void* hip_function,
+    const void* q, const void* k, const void* v,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    float* acc, float* m, float* l, const int64_t acc_strides[3],
+    const int64_t ml_strides[2], int carry_in,
+    const uint8_t* block_mask, const int64_t mask_strides[4], int64_t Bm,
+    int64_t Hm, int log2_block_size, void* blk_workspace,
+    int64_t blk_workspace_bytes, void* stream);
+int bahip_attn_bwd_blk(
+    const void* dout, const void* q, const void* k, const void* v,
+    const float* delta, const float* lse,
+    float* dq, float* dk, float* dv,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t do_strides[3], const int64_t q_strides[3],
+    const int64_t k_strides[3], const int64_t v_strides[3],
+    const int64_t delta_strides[2], const int64_t lse_strides[2],
+    const int64_t dq_strides[3], const int64_t dk_strides[3],
+    const int64_t dv_strides[3],
+    float softmax_scale, int causal, int deterministic, int dtype,
+    const uint8_t* block_mask, const int64_t mask_strides[4], int64_t Bm,
+    int64_t Hm, int log2_block_size, void* blk_workspace,
+    int64_t blk_workspace_bytes, void* stream);
 
 /* The empty state, "no key seen yet", over [B, S] rows of a carry-in state
  * (acc strided {b,s,h}, m/l strided {b,h}, as in bahip_attn_fwd_accum):
