@@ -40,7 +40,8 @@ struct Strides3 {
 };
 
 // per-tensor layout plus cross-tensor consistency vs q: batch/head_dim
-// agree, k/v heads and seqlens agree, q heads are a multiple of the k/v
+// agree (q/k's; v's own width goes to the kernel side as Dv), k/v heads and
+// seqlens agree, q heads are a multiple of the k/v
 // heads (grouped-query: q head h attends kv head h / G), dtypes are equal
 // — a mismatch must raise here, not read out of bounds on device.
 void check_qkv3(const at::Tensor& q, const at::Tensor& k,
@@ -55,8 +56,9 @@ void check_qkv3(const at::Tensor& q, const at::Tensor& k,
   TORCH_CHECK(k.size(2) >= 1 && q.size(2) % k.size(2) == 0,
               "heads mismatch: q heads N=", q.size(2),
               " must be a multiple of kv heads Nk=", k.size(2));
-  TORCH_CHECK(k.size(3) == q.size(3) && v.size(3) == q.size(3),
-              "head_dim mismatch");
+  // v may be narrower or wider than q/k: which (qk, v) width pairs have
+  // kernels is the *_dv entry points' to say, and they name both widths
+  TORCH_CHECK(k.size(3) == q.size(3), "head_dim mismatch");
   TORCH_CHECK(v.size(1) == k.size(1), "k/v seqlen mismatch");
   TORCH_CHECK(q.scalar_type() == k.scalar_type() &&
                   q.scalar_type() == v.scalar_type(),
@@ -238,6 +240,18 @@ at::Tensor attn_seg_prepass(const at::Tensor& q_seg, const at::Tensor& kv_seg) {
   return ws;
 }
 
+// Unequal q/k and v widths have the plain kernel form only.
+void check_plain_dv(int64_t D, int64_t Dv, const SegIds& seg, bool band,
+                    bool capped, const BlkMask& blk) {
+  const char* what = seg.q    ? "q_seg/kv_seg"
+                     : band   ? "band_lo/band_hi"
+                     : capped ? "softcap"
+                     : blk.m  ? "block_mask"
+                              : nullptr;
+  TORCH_CHECK(!what, "head_dim pair (", D, ", ", Dv, ") does not support ",
+              what, " (plain calls only)");
+}
+
 std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k,
                                  const at::Tensor& v, double softmax_scale,
                                  bool causal,
@@ -257,8 +271,19 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k,
   const bool capped = softcap_given(softcap, seg, band);
   const BlkMask blk = blk_mask(block_mask, block_size, blk_ws, q, Sq, Sk, seg,
                                band, softcap);
-  auto o = at::empty({B, Sq, N, D}, q.options().dtype(at::kFloat));
+  const auto Dv = v.size(3);
+  auto o = at::empty({B, Sq, N, Dv}, q.options().dtype(at::kFloat));
   auto lse = at::empty({B, N, Sq}, q.options().dtype(at::kFloat));
+  if (Dv != D) {
+    // unequal widths: the plain call only, V transposed in the kernel
+    check_plain_dv(D, Dv, seg, band, capped, blk);
+    BA_CALL(bahip_attn_fwd_dv(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr<float>(),
+        lse.data_ptr<float>(), B, Sq, Sk, N, k.size(2), D, Dv, Strides3(q),
+        Strides3(k), Strides3(v), (float)softmax_scale, causal ? 1 : 0,
+        dtype_code(q), at::hip::getCurrentHIPStream().stream()));
+    return {o, lse};
+  }
   if (blk.m) {
     // the block-sparse forward transposes V in the kernel: no image workspace
     BA_CALL(bahip_attn_fwd_blk(
@@ -355,6 +380,8 @@ void fwd_accum_call(void* asm_fn, const at::Tensor& q, const at::Tensor& k,
                   && l.scalar_type() == at::kFloat, "state must be fp32");
   TORCH_CHECK(acc.size(1) == Sq && m.size(2) == Sq && l.size(2) == Sq,
               "state rows must match q rows");
+  TORCH_CHECK(acc.dim() == 4 && acc.size(3) == v.size(3),
+              "state acc width must match v's head_dim");
   TORCH_CHECK(acc.stride(3) == 1 && m.stride(2) == 1 && l.stride(2) == 1,
               "state innermost dims must be contiguous");
   int64_t mls[2] = {m.stride(0), m.stride(1)};
@@ -363,6 +390,17 @@ void fwd_accum_call(void* asm_fn, const at::Tensor& q, const at::Tensor& k,
   const bool band = band_given(band_lo, band_hi, seg);
   const BlkMask blk = blk_mask(block_mask, block_size, blk_ws, q, Sq, Sk, seg,
                                band, softcap);
+  if (v.size(3) != D) {
+    check_plain_dv(D, v.size(3), seg, band, softcap != 0.0, blk);
+    BA_CALL(bahip_attn_fwd_accum_dv(
+        asm_fn, q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Sq, Sk, N,
+        k.size(2), D, v.size(3), Strides3(q), Strides3(k), Strides3(v),
+        (float)softmax_scale, causal ? 1 : 0, dtype_code(q),
+        acc.data_ptr<float>(), m.data_ptr<float>(), l.data_ptr<float>(),
+        Strides3(acc), mls, carry_in ? 1 : 0,
+        at::hip::getCurrentHIPStream().stream()));
+    return;
+  }
   if (blk.m) {
     BA_CALL(bahip_attn_fwd_accum_blk(
         nullptr, q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Sq, Sk, N,
@@ -514,7 +552,7 @@ void attn_bwd_accum(const at::Tensor& dout, const at::Tensor& q,
   const auto Sk = k.size(1);
   const SegIds seg = seg_ids(q_seg, kv_seg, q, k);
   TORCH_CHECK(dout.size(0) == B && dout.size(1) == Sq && dout.size(2) == N &&
-                  dout.size(3) == D,
+                  dout.size(3) == v.size(3),
               "dout/q shape mismatch");
   TORCH_CHECK(dout.scalar_type() == q.scalar_type(), "dout/q dtype mismatch");
   TORCH_CHECK(delta.scalar_type() == at::kFloat && lse.scalar_type() == at::kFloat,
@@ -533,6 +571,17 @@ void attn_bwd_accum(const at::Tensor& dout, const at::Tensor& q,
   const bool band = band_given(band_lo, band_hi, seg);
   const BlkMask blk = blk_mask(block_mask, block_size, blk_ws, q, Sq, Sk, seg,
                                band, softcap);
+  if (v.size(3) != D) {
+    check_plain_dv(D, v.size(3), seg, band, softcap != 0.0, blk);
+    BA_CALL(bahip_attn_bwd_dv(
+        dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+        delta.data_ptr<float>(), lse.data_ptr<float>(), dq.data_ptr<float>(),
+        dk.data_ptr<float>(), dv.data_ptr<float>(), B, Sq, Sk, N, k.size(2), D,
+        v.size(3), Strides3(dout), Strides3(q), Strides3(k), Strides3(v), ds,
+        ls, Strides3(dq), Strides3(dk), Strides3(dv), (float)softmax_scale,
+        causal ? 1 : 0, deterministic ? 1 : 0, dtype_code(q), stream));
+    return;
+  }
   if (blk.m) {
     BA_CALL(bahip_attn_bwd_blk(
         dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
@@ -596,7 +645,7 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
   // dk/dv take k/v's head count (Nk <= N with grouped-query heads)
   const auto Nk = k.size(2);
   auto dk = at::zeros({B, Sk, Nk, D}, q.options().dtype(at::kFloat));
-  auto dv = at::zeros({B, Sk, Nk, D}, q.options().dtype(at::kFloat));
+  auto dv = at::zeros({B, Sk, Nk, v.size(3)}, q.options().dtype(at::kFloat));
   attn_bwd_accum(dout, q, k, v, delta, lse, softmax_scale, causal,
                  deterministic, dq, dk, dv, q_seg, kv_seg, band_lo, band_hi,
                  softcap, block_mask, block_size, blk_ws);

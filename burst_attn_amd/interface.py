@@ -291,9 +291,15 @@ def _check_flash_arg(flash):
         )
 
 
+# (q, k, v) widths of multi-head latent attention heads after the latent
+# up-projection: 128 "nope" + 64 rope q/k channels, 128 v/o channels
+_MLA_WIDTHS = (192, 192, 128)
+
+
 def _check_heads(q, k, v):
     """q [B,S,N,H]; k/v [B,S,Nk,H] with N a multiple of Nk (N == Nk is
-    plain multi-head attention)."""
+    plain multi-head attention).  v [B,S,Nk,128] next to H = 192 is the one
+    pair of unequal widths with kernels; o then has v's width."""
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         raise ValueError(
             "q, k, v must be [B, S, heads, head_dim]; got shapes "
@@ -311,7 +317,10 @@ def _check_heads(q, k, v):
             "(grouped-query attention: query head h attends kv head "
             "h // (N // Nk))"
         )
-    if k.shape[3] != q.shape[3] or v.shape[3] != q.shape[3]:
+    widths = (q.shape[3], k.shape[3], v.shape[3])
+    # one pair of unequal widths has kernels: q/k 192 with v 128 (_MLA_WIDTHS)
+    if widths != _MLA_WIDTHS and (widths[1] != widths[0]
+                                  or widths[2] != widths[0]):
         raise ValueError(
             f"head_dim differs: q {q.shape[3]}, k {k.shape[3]}, "
             f"v {v.shape[3]} (N={N}, Nk={Nk})"
@@ -378,6 +387,24 @@ def _check_masks_for_head_dim(q, segment_ids, window):
             f"head_dim 256 with {missing} is not supported yet: the "
             "segment-id and sliding-window tile kernels exist for head_dim "
             "64 and 128 only"
+        )
+
+
+def _check_masks_for_mla_widths(q, v, segment_ids, window, softcap,
+                                block_mask):
+    """q/k 192 with v 128 runs the plain tile kernels only: refuse every
+    masked form here, before any round."""
+    if q.shape[3] == v.shape[3]:
+        return
+    missing = ("segment_ids" if segment_ids is not None
+               else "window_size" if window is not None
+               else "softcap" if softcap > 0
+               else "block_mask" if block_mask is not None else None)
+    if missing:
+        raise ValueError(
+            f"head_dim {q.shape[3]} (q, k) with {v.shape[3]} (v) with "
+            f"{missing} is not supported yet: this shape has the plain tile "
+            "kernels only"
         )
 
 
@@ -491,6 +518,7 @@ def burst_attn_func(
     window = _check_window(window_size, causal, segment_ids)
     _check_masks_for_head_dim(q, segment_ids, window)
     softcap = _check_softcap(softcap, segment_ids, window)
+    _check_masks_for_mla_widths(q, v, segment_ids, window, softcap, block_mask)
     blocks = _check_block_mask(block_mask, block_size, q, k, causal,
                                segment_ids, window, softcap)
     return OpBurstAttn.apply(
@@ -528,6 +556,7 @@ def burst_attn_func_striped(
     window = _check_window(window_size, causal, segment_ids)
     _check_masks_for_head_dim(q, segment_ids, window)
     softcap = _check_softcap(softcap, segment_ids, window)
+    _check_masks_for_mla_widths(q, v, segment_ids, window, softcap, None)
     return OpBurstAttnStrip.apply(
         q, k, v, softmax_scale, flash, causal, optimize_bwd_comm,
         deterministic, process_group, double_group,

@@ -87,6 +87,15 @@ blocks' tiles, so work follows the number of set blocks.  A row that sees no
 key behaves as with ids.  ``blocks`` with ``seg``, ``band`` or ``softcap`` is
 refused.  A caller without a mask passes no ``blocks`` keyword at all.
 
+Unequal widths (multi-head latent attention heads): q and k ``[.., 192]``
+with v ``[.., 128]`` run a kernel set of their own through the same methods,
+with no keyword: the v width is read from v.  o, do, the ``fwd_accum``
+accumulator and dv are then 128 wide, dq and dk 192 wide; ``scale`` is the
+caller's (the interface defaults to ``1/sqrt(192)``).  ``fwd_empty_state(q,
+v_dim=128)`` sizes its accumulator for it.  ``seg``, ``band``, ``softcap`` and
+``blocks`` with this shape are refused.  Any other pair of differing widths
+is an error naming both.
+
 The default provider is the gfx950 HIP extension and FAILS LOUDLY if the
 extension is missing on a GPU machine — there is no CPU/eager fallback in
 the product path.  Tests may inject an oracle-backed provider via
@@ -168,8 +177,22 @@ class HipTileProvider:
         mask2d, bs = blocks
         return {"block_mask": mask2d, "block_size": int(bs)}
 
+    @staticmethod
+    def _check_plain_widths(q, v, seg, band, softcap, blocks):
+        """Unequal q/k and v widths have the plain kernel form only."""
+        if q.shape[3] == v.shape[3]:
+            return
+        for name, given in (("seg", seg is not None), ("band", band is not None),
+                            ("softcap", bool(softcap)),
+                            ("blocks", blocks is not None)):
+            if given:
+                raise RuntimeError(
+                    f"head_dim pair ({q.shape[3]}, {v.shape[3]}) does not "
+                    f"support {name} (plain calls only)")
+
     def fwd(self, q, k, v, scale, causal, seg=None, band=None, softcap=None,
             blocks=None):
+        self._check_plain_widths(q, v, seg, band, softcap, blocks)
         q_seg, kv_seg = seg if seg is not None else (None, None)
         return self._ext.attn_fwd(q, k, v, float(scale), bool(causal),
                                   q_seg, kv_seg, **self._band_kw(band),
@@ -181,6 +204,7 @@ class HipTileProvider:
 
     def bwd(self, do, q, k, v, delta, lse, scale, causal, deterministic,
             seg=None, band=None, softcap=None, blocks=None):
+        self._check_plain_widths(q, v, seg, band, softcap, blocks)
         q_seg, kv_seg = seg if seg is not None else (None, None)
         return self._ext.attn_bwd(
             do, q, k, v, delta, lse, float(scale), bool(causal),
@@ -191,6 +215,7 @@ class HipTileProvider:
 
     def bwd_accum(self, do, q, k, v, delta, lse, scale, causal, deterministic,
                   dq, dk, dv, seg=None, band=None, softcap=None, blocks=None):
+        self._check_plain_widths(q, v, seg, band, softcap, blocks)
         q_seg, kv_seg = seg if seg is not None else (None, None)
         self._ext.attn_bwd_accum(
             do, q, k, v, delta, lse, float(scale), bool(causal),
@@ -208,12 +233,14 @@ class HipTileProvider:
     # row_offset targets the zigzag-half / striped-shift row windows.
     def fwd_accum(self, state, q, k, v, scale, causal, row_offset=0, seg=None,
                   band=None, softcap=None, blocks=None):
+        self._check_plain_widths(q, v, seg, band, softcap, blocks)
         cap_kw = self._cap_kw(softcap, seg, band)
         blk_kw = self._blk_kw(blocks, seg, band, softcap)
         # the .s-built module carries the D=128 production variants only,
         # and no segment, band, soft-capped or block form: with any of them
         # the in-binary kernel runs
-        if (self._asm_fwd and q.shape[3] == 128 and seg is None
+        if (self._asm_fwd and q.shape[3] == 128 and v.shape[3] == 128
+                and seg is None
                 and band is None and not cap_kw and not blk_kw):
             accum = self._ext.attn_fwd_accum_asm
         elif seg is not None or band is not None or cap_kw or blk_kw:
@@ -226,8 +253,9 @@ class HipTileProvider:
             accum = self._ext.attn_fwd_accum
         if state is None:
             assert row_offset == 0, "state is created by a full-row round"
-            B, S, N, D = q.shape
-            acc = torch.empty(B, S, N, D, dtype=torch.float32, device=q.device)
+            B, S, N, _ = q.shape
+            acc = torch.empty(B, S, N, v.shape[3], dtype=torch.float32,
+                              device=q.device)
             m = torch.empty(B, N, S, dtype=torch.float32, device=q.device)
             l = torch.empty(B, N, S, dtype=torch.float32, device=q.device)
             accum(q, k, v, float(scale), bool(causal), acc, m, l, False)
@@ -239,9 +267,11 @@ class HipTileProvider:
         accum(q, k, v, float(scale), bool(causal), accv, mv, lv, True)
         return state
 
-    def fwd_empty_state(self, q):
-        """The state of "no key seen yet" over q's [B, S, N, D] rows."""
+    def fwd_empty_state(self, q, v_dim=None):
+        """The state of "no key seen yet" over q's [B, S, N, D] rows; the
+        accumulator is ``v_dim`` wide where v's width differs from q's."""
         B, S, N, D = q.shape
+        D = D if v_dim is None else v_dim
         acc = torch.empty(B, S, N, D, dtype=torch.float32, device=q.device)
         m = torch.empty(B, N, S, dtype=torch.float32, device=q.device)
         l = torch.empty(B, N, S, dtype=torch.float32, device=q.device)

@@ -150,6 +150,22 @@
  *     forward transposes V in the kernel whatever BA_FWD_VT says and never
  *     uses hip_function.  A block mask together with segment ids, a band or a
  *     cap has no entry point.
+ *   - unequal widths (multi-head latent attention heads): the *_dv entry
+ *     points take the v width Dv after D.  q, k, dq, dk are [.., D]; v, o,
+ *     dO, the carry-in accumulator and dv are [.., Dv]; lse, delta, m and l
+ *     are unchanged.  (D, Dv) = (192, 128) runs a kernel set of its own, 4
+ *     waves per workgroup at one wave per SIMD, 128 rows per workgroup, fp16
+ *     and bf16, causal and rectangular tiles, strided slices, GQA, the same
+ *     state contract (bahip_attn_fwd_state_init, bahip_attn_fwd_finalize and
+ *     bahip_attn_bwd_preprocess are called with D = 128, the width of what
+ *     they touch) and the same bitwise-deterministic backward.  D == Dv is
+ *     exactly the *_gqa entry point.  Any other pair returns
+ *     BAHIP_ERR_UNSUPPORTED with a message naming both widths.  At (192, 128)
+ *     a BA_FWD_* selection other than the default variant, BA_BWD_FUSED=1/2,
+ *     BA_BWD_DK_FLIP=1, BA_DQ_PIPE=1 and a non-null hip_function return
+ *     BAHIP_ERR_UNSUPPORTED naming what was asked; V is transposed in the
+ *     kernel and BA_FWD_VT is not consulted; there is no segment-id, band,
+ *     softcap or block-mask form.  Nothing is launched by a refused call.
  *   - stream is a hipStream_t.
  * Returns 0 on success; nonzero = error.  Every nonzero return sets the
  * calling thread's bahip_last_error() message and every success clears it.
@@ -514,6 +530,42 @@ int bahip_attn_bwd_blk(
     const uint8_t* block_mask, const int64_t mask_strides[4], int64_t Bm,
     int64_t Hm, int log2_block_size, void* blk_workspace,
     int64_t blk_workspace_bytes, void* stream);
+
+/* ---- unequal widths (see "unequal widths" above) -------------------------
+ * bahip_attn_fwd_gqa, bahip_attn_fwd_accum_gqa and bahip_attn_bwd_gqa with the
+ * v width Dv after D. */
+int bahip_attn_fwd_dv(
+    const void* q, const void* k, const void* v,
+    float* o, float* lse,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    int64_t Dv,
+    const int64_t q_strides[3],
+    const int64_t k_strides[3],
+    const int64_t v_strides[3],
+    float softmax_scale, int causal, int dtype,
+    void* stream);
+int bahip_attn_fwd_accum_dv(
+    void* hip_function,
+    const void* q, const void* k, const void* v,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    int64_t Dv,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    float* acc, float* m, float* l, const int64_t acc_strides[3],
+    const int64_t ml_strides[2], int carry_in, void* stream);
+int bahip_attn_bwd_dv(
+    const void* dout, const void* q, const void* k, const void* v,
+    const float* delta, const float* lse,
+    float* dq, float* dk, float* dv,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    int64_t Dv,
+    const int64_t do_strides[3], const int64_t q_strides[3],
+    const int64_t k_strides[3], const int64_t v_strides[3],
+    const int64_t delta_strides[2], const int64_t lse_strides[2],
+    const int64_t dq_strides[3], const int64_t dk_strides[3],
+    const int64_t dv_strides[3],
+    float softmax_scale, int causal, int deterministic, int dtype,
+    void* stream);
 
 /* The empty state, "no key seen yet", over [B, S] rows of a carry-in state
  * (acc strided {b,s,h}, m/l strided {b,h}, as in bahip_attn_fwd_accum):
