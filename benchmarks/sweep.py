@@ -95,6 +95,7 @@ def bench_burst(args, b, s_global, n, d, causal, striped, opt_bwd, steps, warmup
     rank = dist.get_rank()
     s_local = s_global // world
     nk = n if nk is None else nk
+    # fp8 inputs are quantised from the bf16 draw below
     dtype = torch.float16 if args.dtype == "fp16" else torch.bfloat16
     g = torch.Generator().manual_seed(1000 + rank)
     mk = lambda h=n: torch.randn(b, s_local, h, d, generator=g).to(dtype).cuda()
@@ -102,6 +103,19 @@ def bench_burst(args, b, s_global, n, d, causal, striped, opt_bwd, steps, warmup
     func = burst_attn_func_striped if striped else burst_attn_func
     if softcap:
         func = functools.partial(func, softcap=softcap)
+    if args.dtype == "fp8":  # forward leg only: the fp8 kernels have no backward
+        descale = tuple(float(t.float().abs().max()) / 448.0 for t in (q, k, v))
+        q8, k8, v8 = ((t.float() / x).to(torch.float8_e4m3fn)
+                      for t, x in zip((q, k, v), descale))
+        t_f = timeit(lambda: func(q8, k8, v8, None, "cuda", causal,
+                                  descale=descale), steps, warmup)
+        f = flops_fwd(b, s_global, n, d, causal)
+        return {
+            "method": "burst_striped" if striped else "burst",
+            "b": b, "s": s_global, "n": n, "nk": nk, "d": d, "causal": causal,
+            "wsize": world, "dtype": "fp8", "fwd_ms": round(t_f * 1e3, 2),
+            "fwd_tflops_per_gpu": round(f / t_f / 1e12 / world, 2),
+        }
 
     def fwd():
         with torch.no_grad():
@@ -428,7 +442,9 @@ def main():
                    default="quick")
     p.add_argument("--steps", type=int, default=3)
     p.add_argument("--warmup", type=int, default=1)
-    p.add_argument("--dtype", choices=["fp16", "bf16"], default="fp16")
+    p.add_argument("--dtype", choices=["fp16", "bf16", "fp8"], default="fp16",
+                   help="fp8: float8_e4m3fn q/k/v, forward legs only (the "
+                        "quick, ring, batch and gqa configs)")
     p.add_argument("--out", default="results_mi355x.jsonl")
     p.add_argument("--heads", type=int, default=32)
     p.add_argument("--head-dim", type=int, default=128,
@@ -465,6 +481,9 @@ def main():
 
     rows = []
     n, d = args.heads, args.head_dim
+    if args.dtype == "fp8" and (args.window or args.softcap or args.configs
+                                not in ("quick", "ring", "batch", "gqa")):
+        p.error("--dtype fp8 runs the quick, ring, batch and gqa configs only")
     if args.window:
         if world != 1:
             p.error("--window is a one-GPU measurement")
@@ -498,7 +517,7 @@ def main():
             for causal in (False, True):
                 rows.append(bench_burst(args, 1, s, n, d, causal, False, causal,
                                         args.steps, args.warmup, nk))
-        if world == 1:
+        if world == 1 and args.dtype != "fp8":
             rows.append(bench_single_flash(args, 1, 65536, n, d, False,
                                            args.steps, args.warmup))
     elif args.configs == "ring":  # the README seq sweep (per world size)
@@ -529,7 +548,7 @@ def main():
             for h in dict.fromkeys((n, nk)):
                 rows.append(bench_burst(args, 1, args.seq, n, d, causal, False,
                                         causal, args.steps, args.warmup, h))
-            if world == 1:
+            if world == 1 and args.dtype != "fp8":
                 for g_launch in (False, True):
                     rows.append(bench_bwd_tile(args, 1, args.seq, n, nk, d,
                                                causal, g_launch, args.steps,

@@ -19,7 +19,8 @@ DEVICE_SOURCES = ["attn_fwd.hip", "attn_bwd.hip", "probes.hip",
                   "attn_d256_fwd.hip", "attn_d256_bwd.hip",
                   "attn_fwd_softcap.hip", "attn_bwd_softcap.hip",
                   "attn_fwd_blk.hip", "attn_bwd_blk.hip",
-                  "attn_hd192_fwd.hip", "attn_hd192_bwd.hip"]
+                  "attn_hd192_fwd.hip", "attn_hd192_bwd.hip",
+                  "attn_fp8_fwd.hip"]
 # Per-source compiler flags.  The head_dim 256 kernels are built without
 # packed fp32 VALU ops (v_pk_mul_f32 and kin): the accumulator rescale is
 # the one place the compiler would form them, and scalar fp32 ops keep the
@@ -38,6 +39,7 @@ EXTRA_FLAGS = {
     "attn_bwd_blk.hip": _NO_PK_F32,
     "attn_hd192_fwd.hip": _NO_PK_F32,
     "attn_hd192_bwd.hip": _NO_PK_F32,
+    "attn_fp8_fwd.hip": _NO_PK_F32,
 }
 # sources a source includes, beyond the headers: rebuilt when those change
 SOURCE_DEPS = {

@@ -20,14 +20,22 @@ int dtype_code(const at::Tensor& t) {
   return -1;
 }
 
+// FP8 (e4m3) q/k/v: a forward of its own (the *_f8 entry points), plain calls
+// only, no backward.
+bool is_fp8(const at::Tensor& t) {
+  return t.scalar_type() == at::kFloat8_e4m3fn;
+}
+
 void check_qkv(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
   TORCH_CHECK(t.dim() == 4, name, " must be [B,S,N,D]");
   TORCH_CHECK(t.stride(3) == 1, name, " head_dim must be contiguous");
-  TORCH_CHECK(t.stride(1) % 8 == 0, name,
-              " seq stride must be a multiple of 8 elements (16B alignment)");
-  TORCH_CHECK(t.stride(2) % 8 == 0, name,
-              " head stride must be a multiple of 8 elements");
+  // rows are read 16 bytes at a time: 8 two-byte elements, 16 fp8 ones
+  const int64_t e = is_fp8(t) ? 16 : 8;
+  TORCH_CHECK(t.stride(1) % e == 0, name, " seq stride must be a multiple of ",
+              e, " elements (16B alignment)");
+  TORCH_CHECK(t.stride(2) % e == 0, name,
+              " head stride must be a multiple of ", e, " elements");
 }
 
 // {batch, seq, head} element strides of a [B,S,N,D] tensor, as the C ABI
@@ -65,6 +73,35 @@ void check_qkv3(const at::Tensor& q, const at::Tensor& k,
               "q/k/v dtype mismatch");
 }
 
+using Descale = c10::optional<std::tuple<double, double, double>>;
+
+void check_fp8_plain(const c10::optional<at::Tensor>& q_seg,
+                     const c10::optional<at::Tensor>& kv_seg,
+                     const c10::optional<int64_t>& band_lo,
+                     const c10::optional<int64_t>& band_hi, double softcap,
+                     const c10::optional<at::Tensor>& block_mask) {
+  const char* what = (q_seg.has_value() || kv_seg.has_value()) ? "q_seg/kv_seg"
+                     : (band_lo.has_value() || band_hi.has_value())
+                         ? "band_lo/band_hi"
+                     : softcap != 0.0         ? "softcap"
+                     : block_mask.has_value() ? "block_mask"
+                                              : nullptr;
+  TORCH_CHECK(!what, "fp8 (float8_e4m3fn) inputs do not support ", what,
+              " (plain calls only)");
+}
+
+// The *_f8 entry points carry one D for q, k and v, so the v width is this
+// layer's to check before anything is sized or launched.
+void check_fp8_widths(const at::Tensor& q, const at::Tensor& v) {
+  TORCH_CHECK(v.size(3) == q.size(3), "fp8 (float8_e4m3fn) inputs need equal "
+              "q/k and v head_dim, got ", q.size(3), " and ", v.size(3));
+}
+
+void check_no_fp8_bwd(const at::Tensor& q) {
+  TORCH_CHECK(!is_fp8(q), "burst_attn: fp8 (float8_e4m3fn) inputs have no "
+                          "backward: the fp8 kernels are forward only");
+}
+
 #define BA_CALL(expr)                                                      \
   do {                                                                     \
     int rc_ = (expr);                                                      \
@@ -81,6 +118,14 @@ at::Tensor fwd_workspace(const at::Tensor& q, const at::Tensor& k) {
       q.size(0), q.size(1), k.size(1), q.size(2), k.size(2), q.size(3));
   if (bytes <= 0) return at::Tensor();
   return at::empty({bytes}, q.options().dtype(at::kByte));
+}
+
+// Workspace for the permuted V^T image of an fp8 call (never empty, so that
+// data_ptr() is a pointer the launcher can check).
+at::Tensor fp8_workspace(const at::Tensor& k) {
+  const int64_t bytes = bahip_attn_fwd_f8_workspace_bytes(
+      k.size(0), k.size(1), k.size(2), k.size(3));
+  return at::empty({bytes > 0 ? bytes : 16}, k.options().dtype(at::kByte));
 }
 
 // Segment ids of a call: both or neither; int32 [B, Sq] / [B, Sk] with a
@@ -262,10 +307,29 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k,
                                  double softcap,
                                  const c10::optional<at::Tensor>& block_mask,
                                  int64_t block_size,
-                                 const c10::optional<at::Tensor>& blk_ws) {
+                                 const c10::optional<at::Tensor>& blk_ws,
+                                 const Descale& descale) {
   check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
+  if (is_fp8(q)) {
+    check_fp8_plain(q_seg, kv_seg, band_lo, band_hi, softcap, block_mask);
+    check_fp8_widths(q, v);
+    const auto [dq, dk, dv] = descale.value_or(std::make_tuple(1.0, 1.0, 1.0));
+    auto o = at::empty({B, Sq, N, D}, q.options().dtype(at::kFloat));
+    auto lse = at::empty({B, N, Sq}, q.options().dtype(at::kFloat));
+    auto ws = fp8_workspace(k);
+    BA_CALL(bahip_attn_fwd_f8(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr<float>(),
+        lse.data_ptr<float>(), B, Sq, Sk, N, k.size(2), D, Strides3(q),
+        Strides3(k), Strides3(v), (float)softmax_scale, causal ? 1 : 0,
+        BAHIP_F8E4M3, (float)dq, (float)dk, (float)dv, ws.data_ptr(),
+        ws.numel(), at::hip::getCurrentHIPStream().stream()));
+    return {o, lse};
+  }
+  TORCH_CHECK(!descale.has_value(),
+              "descale is for fp8 (float8_e4m3fn) inputs only, got ",
+              q.scalar_type());
   const SegIds seg = seg_ids(q_seg, kv_seg, q, k);
   const bool band = band_given(band_lo, band_hi, seg);
   const bool capped = softcap_given(softcap, seg, band);
@@ -371,10 +435,18 @@ void fwd_accum_call(void* asm_fn, const at::Tensor& q, const at::Tensor& k,
                     double softcap = 0.0,
                     const c10::optional<at::Tensor>& block_mask = c10::nullopt,
                     int64_t block_size = 64,
-                    const c10::optional<at::Tensor>& blk_ws = c10::nullopt) {
+                    const c10::optional<at::Tensor>& blk_ws = c10::nullopt,
+                    const Descale& descale = c10::nullopt) {
   check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
+  if (is_fp8(q)) {
+    check_fp8_plain(q_seg, kv_seg, band_lo, band_hi, softcap, block_mask);
+    check_fp8_widths(q, v);
+  } else
+    TORCH_CHECK(!descale.has_value(),
+                "descale is for fp8 (float8_e4m3fn) inputs only, got ",
+                q.scalar_type());
   const SegIds seg = seg_ids(q_seg, kv_seg, q, k);
   TORCH_CHECK(acc.scalar_type() == at::kFloat && m.scalar_type() == at::kFloat
                   && l.scalar_type() == at::kFloat, "state must be fp32");
@@ -387,6 +459,18 @@ void fwd_accum_call(void* asm_fn, const at::Tensor& q, const at::Tensor& k,
   int64_t mls[2] = {m.stride(0), m.stride(1)};
   TORCH_CHECK(l.stride(0) == mls[0] && l.stride(1) == mls[1],
               "m/l stride mismatch");
+  if (is_fp8(q)) {
+    const auto [dq, dk, dv] = descale.value_or(std::make_tuple(1.0, 1.0, 1.0));
+    auto ws = fp8_workspace(k);
+    BA_CALL(bahip_attn_fwd_accum_f8(
+        asm_fn, q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Sq, Sk, N,
+        k.size(2), D, Strides3(q), Strides3(k), Strides3(v),
+        (float)softmax_scale, causal ? 1 : 0, BAHIP_F8E4M3,
+        acc.data_ptr<float>(), m.data_ptr<float>(), l.data_ptr<float>(),
+        Strides3(acc), mls, carry_in ? 1 : 0, (float)dq, (float)dk, (float)dv,
+        ws.data_ptr(), ws.numel(), at::hip::getCurrentHIPStream().stream()));
+    return;
+  }
   const bool band = band_given(band_lo, band_hi, seg);
   const BlkMask blk = blk_mask(block_mask, block_size, blk_ws, q, Sq, Sk, seg,
                                band, softcap);
@@ -455,10 +539,11 @@ void attn_fwd_accum(const at::Tensor& q, const at::Tensor& k,
                     const c10::optional<int64_t>& band_hi, double softcap,
                     const c10::optional<at::Tensor>& block_mask,
                     int64_t block_size,
-                    const c10::optional<at::Tensor>& blk_ws) {
+                    const c10::optional<at::Tensor>& blk_ws,
+                    const Descale& descale) {
   fwd_accum_call(nullptr, q, k, v, softmax_scale, causal, acc, m, l, carry_in,
                  q_seg, kv_seg, band_lo, band_hi, softcap, block_mask,
-                 block_size, blk_ws);
+                 block_size, blk_ws, descale);
 }
 
 // The empty carry-in state ("no key seen yet") written into acc [B,S,N,D],
@@ -546,6 +631,7 @@ void attn_bwd_accum(const at::Tensor& dout, const at::Tensor& q,
                     const c10::optional<at::Tensor>& block_mask,
                     int64_t block_size,
                     const c10::optional<at::Tensor>& blk_ws) {
+  check_no_fp8_bwd(q);
   check_qkv(dout, "dout");
   check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
@@ -638,6 +724,7 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
                                  const c10::optional<at::Tensor>& block_mask,
                                  int64_t block_size,
                                  const c10::optional<at::Tensor>& blk_ws) {
+  check_no_fp8_bwd(q);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
   // zero-filled: the kernels accumulate, so this equals fresh outputs
@@ -682,7 +769,9 @@ void attn_fwd_accum_asm(const at::Tensor& q, const at::Tensor& k,
                         const at::Tensor& v, double softmax_scale,
                         bool causal, at::Tensor& acc, at::Tensor& m,
                         at::Tensor& l, bool carry_in) {
-  const int dt = dtype_code(q);
+  // fp8 has no module kernel: the bound function goes on to the *_f8 entry
+  // point, whose refusal of a module kernel names it, and nothing is launched
+  const int dt = is_fp8(q) ? 0 : dtype_code(q);
   TORCH_CHECK(g_asm_fn[dt] != nullptr, "asm forward not loaded");
   TORCH_CHECK(q.size(3) == 128, "asm forward: D=128 variants only");
   fwd_accum_call(g_asm_fn[dt], q, k, v, softmax_scale, causal, acc, m, l,
@@ -698,6 +787,18 @@ at::Tensor mfma_probe(const at::Tensor& a, const at::Tensor& b) {
   auto stream = at::hip::getCurrentHIPStream().stream();
   BA_CALL(bahip_mfma_probe(a.data_ptr(), b.data_ptr(), d.data_ptr<float>(),
                            dtype_code(a), stream));
+  return d;
+}
+
+at::Tensor fp8_mfma_probe(const at::Tensor& a, const at::Tensor& b) {
+  TORCH_CHECK(a.is_cuda() && b.is_cuda() && a.is_contiguous() &&
+              b.is_contiguous() && is_fp8(a) && is_fp8(b));
+  TORCH_CHECK(a.sizes() == at::IntArrayRef({32, 64}) &&
+              b.sizes() == at::IntArrayRef({64, 32}));
+  auto d = at::zeros({32, 32}, a.options().dtype(at::kFloat));
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  BA_CALL(bahip_fp8_mfma_probe(a.data_ptr(), b.data_ptr(), d.data_ptr<float>(),
+                               stream));
   return d;
 }
 
@@ -717,7 +818,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("kv_seg") = py::none(), py::arg("band_lo") = py::none(),
         py::arg("band_hi") = py::none(), py::arg("softcap") = 0.0,
         py::arg("block_mask") = py::none(), py::arg("block_size") = 64,
-        py::arg("blk_ws") = py::none());
+        py::arg("blk_ws") = py::none(), py::arg("descale") = py::none());
   m.def("attn_fwd_accum", &attn_fwd_accum,
         "carry-in accumulator fwd tile (in-kernel LSE merge)", py::arg("q"),
         py::arg("k"), py::arg("v"), py::arg("softmax_scale"),
@@ -726,7 +827,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("kv_seg") = py::none(), py::arg("band_lo") = py::none(),
         py::arg("band_hi") = py::none(), py::arg("softcap") = 0.0,
         py::arg("block_mask") = py::none(), py::arg("block_size") = 64,
-        py::arg("blk_ws") = py::none());
+        py::arg("blk_ws") = py::none(), py::arg("descale") = py::none());
+  m.def("attn_fp8_p_scale", [] { return (double)BAHIP_F8_P_SCALE; },
+        "the power of two the fp8 forward multiplies P by before it rounds "
+        "P to e4m3");
   m.def("attn_fwd_state_init", &attn_fwd_state_init,
         "write the empty carry-in state (no key seen yet) into acc, m, l");
   m.def("attn_seg_prepass", &attn_seg_prepass,
@@ -771,6 +875,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("block_mask") = py::none(), py::arg("block_size") = 64,
         py::arg("blk_ws") = py::none());
   m.def("mfma_probe", &mfma_probe, "32x32x16 MFMA layout probe");
+  m.def("fp8_mfma_probe", &fp8_mfma_probe, "32x32x64 fp8 MFMA layout probe");
   m.def("tr16_probe", &tr16_probe, "ds_read_tr16_b64 semantics probe");
   m.def("attn_fwd_asm_load", &attn_fwd_asm_load,
         "load the .s-built forward hsaco (round-3 on-ramp)");

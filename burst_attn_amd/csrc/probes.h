@@ -12,6 +12,10 @@ extern "C" {
 int bahip_mfma_probe(const void* a, const void* b, float* d, int dtype,
                      void* stream);
 
+// d[32][32] = a[32][64] * b[64][32] through one 32x32x64 fp8 MFMA with unit
+// scales; a, b dense row-major e4m3 bytes, d fp32.
+int bahip_fp8_mfma_probe(const void* a, const void* b, float* d, void* stream);
+
 // out[64 lanes][4] = what ds_read_tr16_b64 returns for address pattern
 // `mode` (0..4) over an LDS image holding its own element indices.
 int bahip_tr16_probe(int mode, int* out, void* stream);

@@ -4,6 +4,7 @@
 // attention kernels only.
 
 #include "attn_common.h"
+#include "attn_fp8.h"
 #include "attn_host.h"
 #include "probes.h"
 
@@ -52,7 +53,41 @@ __global__ void tr16_probe_kernel(int mode, int* out) {
   for (int j = 0; j < 4; ++j) out[l * 4 + j] = (int)(unsigned short)v[j];
 }
 
+// ---- K = 64 fp8 MFMA layout probe: D = A*B for one 32x32x64 tile through
+// ba_fp8_mma (unit E8M0 scales), with A,B,D moved per the layout attn_fp8.h
+// states.  a: [32][64] row-major, b: [64][32] row-major, both e4m3 bytes;
+// d: [32][32] row-major fp32.
+__global__ void fp8_mfma_probe_kernel(const unsigned char* a,
+                                      const unsigned char* b, float* d) {
+  const int lane = threadIdx.x & 63;
+  const int l31 = lane & 31, hi = lane >> 5;
+  i32x8_t af, bf;
+#pragma unroll
+  for (int w = 0; w < 8; ++w) {
+    unsigned int aw = 0, bw = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int kk = 32 * hi + 4 * w + e;  // byte 4 w + e of half hi
+      aw |= (unsigned int)a[l31 * 64 + kk] << (8 * e);  // A[row=l31][k]
+      bw |= (unsigned int)b[kk * 32 + l31] << (8 * e);  // B[k][col=l31]
+    }
+    af[w] = (int)aw;
+    bf[w] = (int)bw;
+  }
+  f32x16_t c = (f32x16_t)(0.f);
+  c = ba_fp8_mma(af, bf, c);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) d[ba_crow(r, hi) * 32 + l31] = c[r];
+}
+
 }  // namespace
+
+extern "C" int bahip_fp8_mfma_probe(const void* a, const void* b, float* d,
+                                    void* stream) {
+  fp8_mfma_probe_kernel<<<1, 64, 0, (hipStream_t)stream>>>(
+      (const unsigned char*)a, (const unsigned char*)b, d);
+  return ba_launch_status();
+}
 
 extern "C" int bahip_tr16_probe(int mode, int* out, void* stream) {
   tr16_probe_kernel<<<1, 64, 0, (hipStream_t)stream>>>(mode, out);

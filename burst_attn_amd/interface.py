@@ -76,6 +76,16 @@ payloads nor the provider calls change.  A mask together with
 ``segment_ids``, an effective window, a cap, head_dim 256 or the striped op
 is refused.
 
+FP8: with q, k, v of ``torch.float8_e4m3fn`` (head_dim 128) the trailing
+keyword ``descale=(sq, sk, sv)`` gives the per-tensor descales (real values
+``q8 * sq`` and so on; three positive finite Python floats every rank knows,
+default ones).  The call is forward only: o is ``torch.bfloat16``, nothing is
+saved, k and v travel the ring as ``uint8`` views of their bytes and every
+round hands the tile provider ``descale=``.  Inputs that require grad,
+``segment_ids``, an effective window, a cap, a block mask, another head_dim
+and a malformed ``descale`` are refused before any round, and so is
+``descale`` with 16-bit inputs, whose calls are otherwise unchanged.
+
 The two causal load-balancing layouts (see oracle/partition.py) run the
 same code: ``OpBurstAttn`` (zigzag: rank r holds global chunks [r] and
 [2W-1-r]) and ``OpBurstAttnStrip`` (striped: token t on rank t mod W) only
@@ -485,10 +495,62 @@ def _check_block_mask(block_mask, block_size, q, k, causal, segment_ids,
     return block_mask.to(torch.uint8).contiguous(), bs
 
 
-def _op_args(ids, window, softcap, blocks=None):
+_FP8 = torch.float8_e4m3fn
+
+
+def _check_fp8(q, k, v, descale, segment_ids, window, softcap, block_mask):
+    """None with 16-bit inputs, else the fp8 call's ``(sq, sk, sv)`` floats.
+    Everything an fp8 call cannot have is refused here, before any round."""
+    dtypes = (q.dtype, k.dtype, v.dtype)
+    if _FP8 not in dtypes:
+        if descale is not None:
+            raise ValueError(
+                "descale is for fp8 (torch.float8_e4m3fn) q, k, v only, got "
+                f"q of {q.dtype}"
+            )
+        return None
+    if dtypes != (_FP8,) * 3:
+        raise ValueError(
+            f"fp8: q, k and v must all be torch.float8_e4m3fn, got {dtypes}"
+        )
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+        raise ValueError(
+            "fp8 inputs that require grad are not supported: the fp8 kernels "
+            "are forward only (there is no fp8 backward)"
+        )
+    other = ("segment_ids" if segment_ids is not None
+             else "window_size" if window is not None
+             else "softcap" if softcap > 0
+             else "block_mask" if block_mask is not None else None)
+    if other:
+        raise ValueError(
+            f"fp8 with {other} is not supported yet: fp8 inputs have the "
+            "plain tile kernels only"
+        )
+    if (q.shape[3], k.shape[3], v.shape[3]) != (128, 128, 128):
+        raise ValueError(
+            f"fp8 supports head_dim 128 only, got q {q.shape[3]}, "
+            f"k {k.shape[3]}, v {v.shape[3]}"
+        )
+    if descale is None:
+        return (1.0, 1.0, 1.0)
+    if (not isinstance(descale, (tuple, list)) or len(descale) != 3
+            or any(isinstance(x, bool) or not isinstance(x, (int, float))
+                   or not math.isfinite(x) or x <= 0 for x in descale)):
+        raise ValueError(
+            "descale must be (sq, sk, sv), three positive finite Python "
+            f"floats, got {descale!r}"
+        )
+    return tuple(float(x) for x in descale)
+
+
+def _op_args(ids, window, softcap, blocks=None, descale=None):
     """The trailing arguments of the two ops: the ids always, the window, the
-    cap and the block mask only when given, so that a call without them
-    applies the op with the argument list it had before they existed."""
+    cap, the block mask and the fp8 descales only when given, so that a call
+    without them applies the op with the argument list it had before they
+    existed."""
+    if descale is not None:  # never with ids, a window, a cap or a mask
+        return (None, None, 0.0, None, 64, descale)
     if blocks is not None:
         return (ids, None, 0.0, *blocks)  # never with ids, a window or a cap
     if softcap > 0:
@@ -513,18 +575,22 @@ def burst_attn_func(
     softcap: float = 0.0,
     block_mask: torch.Tensor = None,
     block_size: int = 64,
+    descale=None,
 ):
     _check_heads(q, k, v)
     window = _check_window(window_size, causal, segment_ids)
     _check_masks_for_head_dim(q, segment_ids, window)
     softcap = _check_softcap(softcap, segment_ids, window)
     _check_masks_for_mla_widths(q, v, segment_ids, window, softcap, block_mask)
+    descale = _check_fp8(q, k, v, descale, segment_ids, window, softcap,
+                         block_mask)
     blocks = _check_block_mask(block_mask, block_size, q, k, causal,
                                segment_ids, window, softcap)
     return OpBurstAttn.apply(
         q, k, v, softmax_scale, flash, causal, optimize_bwd_comm,
         deterministic, process_group, double_group,
-        *_op_args(_check_segment_ids(segment_ids, q), window, softcap, blocks),
+        *_op_args(_check_segment_ids(segment_ids, q), window, softcap, blocks,
+                  descale),
     )
 
 
@@ -545,6 +611,7 @@ def burst_attn_func_striped(
     softcap: float = 0.0,
     block_mask: torch.Tensor = None,
     block_size: int = 64,
+    descale=None,
 ):
     _check_heads(q, k, v)
     if block_mask is not None:
@@ -557,10 +624,12 @@ def burst_attn_func_striped(
     _check_masks_for_head_dim(q, segment_ids, window)
     softcap = _check_softcap(softcap, segment_ids, window)
     _check_masks_for_mla_widths(q, v, segment_ids, window, softcap, None)
+    descale = _check_fp8(q, k, v, descale, segment_ids, window, softcap, None)
     return OpBurstAttnStrip.apply(
         q, k, v, softmax_scale, flash, causal, optimize_bwd_comm,
         deterministic, process_group, double_group,
-        *_op_args(_check_segment_ids(segment_ids, q), window, softcap),
+        *_op_args(_check_segment_ids(segment_ids, q), window, softcap,
+                  descale=descale),
     )
 
 
@@ -568,18 +637,24 @@ def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
                   causal=False, optimize_bwd_comm=False, deterministic=False,
                   process_group=None, double_group=[None, None],
                   segment_ids=None, window=None, softcap=0.0, block_mask=None,
-                  block_size=64):
+                  block_size=64, descale=None):
     """Forward of both layouts: q stays, {k, v} travel the ring (with the
     kv ids, when there are segment ids).  With a window every round is the
     sub-tiles of ``window_tiles``, merged into a state that starts empty; with
     a block mask those of ``block_tiles``, each on its view of the rank's slab.
-    With a cap every round's tile call carries it."""
+    With a cap every round's tile call carries it.  With fp8 inputs (``descale``
+    given) k and v travel as uint8 views of their bytes, every round's tile
+    call carries the descales, o is bf16 and nothing is saved."""
     _check_flash_arg(flash)
     ctx.segment_ids = ids = segment_ids
     ctx.blocks = None if block_mask is None else (block_mask, block_size)
     ctx.window = window
     ctx.softcap = softcap
     cap = {"softcap": softcap} if softcap > 0 else {}
+    if descale is not None:
+        cap = {"descale": descale}  # never together with a softcap
+        # the wire carries bytes: RCCL and gloo need no fp8 support
+        k, v = k.view(torch.uint8), v.view(torch.uint8)
     ctx.dq_group = double_group
     if isinstance(double_group[0], tuple):
         # [(group, dq_group), (group2, dq_group2)] — separate backward dq
@@ -598,7 +673,8 @@ def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
     P = get_tile_provider()
     ring = Ring(process_group, double_group)
     W, rank = ring.world_size, ring.rank
-    ori_k, ori_v = replicate(k), replicate(v)
+    if descale is None:
+        ori_k, ori_v = replicate(k), replicate(v)
     comm_bufs = [torch.empty_like(k), torch.empty_like(v)]
     kv_ids = None
     if ids is not None:
@@ -648,7 +724,10 @@ def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
                             block_size))
         else:
             seg = {} if ids is None else {"seg": (ids[:, qw], kv_ids[:, kw])}
-            state = P.fwd_accum(state, q[:, qw], k[:, kw], v[:, kw], scale,
+            kt, vt = k[:, kw], v[:, kw]
+            if descale is not None:
+                kt, vt = kt.view(_FP8), vt.view(_FP8)
+            state = P.fwd_accum(state, q[:, qw], kt, vt, scale,
                                 tile_causal, row_offset=qw.start or 0, **seg,
                                 **cap)
         if r != W:
@@ -659,6 +738,8 @@ def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
             ring.wait()
     _logger.info("fwd record of rank %d: %s", get_rank(), record)
     # o in q.dtype, lse [B,N,S] fp32 (reference :250-252 semantics)
+    if descale is not None:  # forward only: bf16 o, nothing saved
+        return P.fwd_finalize(state, torch.bfloat16)[0]
     out, lse = P.fwd_finalize(state, q.dtype)
     ctx.save_for_backward(q, ori_k, ori_v, lse, replicate(out))
     return out

@@ -96,6 +96,16 @@ v_dim=128)`` sizes its accumulator for it.  ``seg``, ``band``, ``softcap`` and
 ``blocks`` with this shape are refused.  Any other pair of differing widths
 is an error naming both.
 
+FP8 (``torch.float8_e4m3fn`` q, k, v, the gfx950 native OCP e4m3): ``fwd`` and
+``fwd_accum`` run a forward of their own on the K = 64 fp8 MFMA and take an
+optional keyword ``descale=(sq, sk, sv)``, three positive finite Python
+floats: the real values are ``q8 * sq`` and so on, per tensor.  head_dim 128,
+equal widths.  o, the state and lse are fp32 in real units exactly as with
+16-bit inputs, so ``fwd_empty_state``, ``fwd_finalize`` and ``merge`` are
+unchanged.  There is no backward; ``seg``, ``band``, ``softcap`` and
+``blocks`` with fp8 are refused.  A caller without fp8 inputs passes no
+``descale`` keyword at all.
+
 The default provider is the gfx950 HIP extension and FAILS LOUDLY if the
 extension is missing on a GPU machine — there is no CPU/eager fallback in
 the product path.  Tests may inject an oracle-backed provider via
@@ -190,9 +200,30 @@ class HipTileProvider:
                     f"head_dim pair ({q.shape[3]}, {v.shape[3]}) does not "
                     f"support {name} (plain calls only)")
 
+    @staticmethod
+    def _fp8_kw(q, descale, seg, band, softcap, blocks):
+        """The extension's keyword of an fp8 call; none with 16-bit inputs."""
+        if q.dtype != torch.float8_e4m3fn:
+            if descale is not None:
+                raise RuntimeError(
+                    f"descale is for fp8 inputs only, q is {q.dtype}")
+            return {}
+        for name, given in (("seg", seg is not None), ("band", band is not None),
+                            ("softcap", bool(softcap)),
+                            ("blocks", blocks is not None)):
+            if given:
+                raise RuntimeError(
+                    f"fp8 inputs do not support {name} (plain calls only)")
+        sq, sk, sv = (1.0, 1.0, 1.0) if descale is None else descale
+        return {"descale": (float(sq), float(sk), float(sv))}
+
     def fwd(self, q, k, v, scale, causal, seg=None, band=None, softcap=None,
-            blocks=None):
+            blocks=None, descale=None):
         self._check_plain_widths(q, v, seg, band, softcap, blocks)
+        fp8_kw = self._fp8_kw(q, descale, seg, band, softcap, blocks)
+        if fp8_kw:
+            return self._ext.attn_fwd(q, k, v, float(scale), bool(causal),
+                                      **fp8_kw)
         q_seg, kv_seg = seg if seg is not None else (None, None)
         return self._ext.attn_fwd(q, k, v, float(scale), bool(causal),
                                   q_seg, kv_seg, **self._band_kw(band),
@@ -232,14 +263,17 @@ class HipTileProvider:
     # running max, l fp32 [B,N,S] running sum) over the rank's FULL chunk;
     # row_offset targets the zigzag-half / striped-shift row windows.
     def fwd_accum(self, state, q, k, v, scale, causal, row_offset=0, seg=None,
-                  band=None, softcap=None, blocks=None):
+                  band=None, softcap=None, blocks=None, descale=None):
         self._check_plain_widths(q, v, seg, band, softcap, blocks)
+        fp8_kw = self._fp8_kw(q, descale, seg, band, softcap, blocks)
         cap_kw = self._cap_kw(softcap, seg, band)
         blk_kw = self._blk_kw(blocks, seg, band, softcap)
         # the .s-built module carries the D=128 production variants only,
         # and no segment, band, soft-capped or block form: with any of them
         # the in-binary kernel runs
-        if (self._asm_fwd and q.shape[3] == 128 and v.shape[3] == 128
+        if fp8_kw:  # a kernel set of its own, never the module kernel
+            accum = functools.partial(self._ext.attn_fwd_accum, **fp8_kw)
+        elif (self._asm_fwd and q.shape[3] == 128 and v.shape[3] == 128
                 and seg is None
                 and band is None and not cap_kw and not blk_kw):
             accum = self._ext.attn_fwd_accum_asm

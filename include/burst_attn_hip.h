@@ -166,6 +166,28 @@
  *     BAHIP_ERR_UNSUPPORTED naming what was asked; V is transposed in the
  *     kernel and BA_FWD_VT is not consulted; there is no segment-id, band,
  *     softcap or block-mask form.  Nothing is launched by a refused call.
+ *   - FP8 (OCP e4m3, the gfx950 native 8-bit format): the *_f8 entry points
+ *     are a forward of their own for q, k, v of dtype BAHIP_F8E4M3 at
+ *     D = 128 (equal widths), causal and rectangular tiles, strided slices
+ *     (strides in elements = bytes, seq and head strides multiples of 16),
+ *     GQA, stateless and carry-in.  Real values are q8 * descale_q and so on
+ *     (per-tensor descales, positive and finite); o / acc, m and l are fp32
+ *     in real units with the state contract of every other forward, so
+ *     bahip_attn_fwd_state_init and bahip_attn_fwd_finalize serve them at
+ *     D = 128.  A pre-pass on `stream` writes the permuted V^T image of this
+ *     call (attn_fp8.h) into `workspace`, at least
+ *     bahip_attn_fwd_f8_workspace_bytes() bytes; a null or short one returns
+ *     BAHIP_ERR_WORKSPACE.  A descale that is not positive and finite returns
+ *     BAHIP_ERR_DESCALE, and so does one whose derived multipliers (the
+ *     score scale, 16 / descale_v, descale_v / 16) are not.  The entry points
+ *     carry one D: v rows are read D bytes wide, so a caller with a v of
+ *     another width must refuse it itself.  A misaligned base or stride
+ *     returns BAHIP_ERR_UNSUPPORTED naming the tensor and the stride.
+ *     D != 128, another dtype code, a BA_FWD_* selection
+ *     other than the default variant and a non-null hip_function return
+ *     BAHIP_ERR_UNSUPPORTED naming what was asked.  Nothing is launched by a
+ *     refused call.  There is no backward and no mask form.  Every other
+ *     entry point keeps refusing BAHIP_F8E4M3 as an unknown dtype code.
  *   - stream is a hipStream_t.
  * Returns 0 on success; nonzero = error.  Every nonzero return sets the
  * calling thread's bahip_last_error() message and every success clears it.
@@ -181,6 +203,7 @@ extern "C" {
 
 #define BAHIP_F16 0
 #define BAHIP_BF16 1
+#define BAHIP_F8E4M3 2 /* the *_f8 entry points only */
 
 #define BAHIP_ERR_CAUSAL_SHAPE 1001   /* causal with Sq != Sk */
 #define BAHIP_ERR_UNSUPPORTED 1002    /* head_dim not 64/128/256, dtype, a
@@ -202,6 +225,9 @@ extern "C" {
 #define BAHIP_ERR_BLOCK_MASK 1009     /* block mask null, BS < 64 or not a
                                          power of two, Bm not in {1, B}, Hm
                                          not in {1, Nk} */
+
+#define BAHIP_ERR_DESCALE 1010        /* an fp8 descale not positive or not
+                                         finite */
 
 const char* bahip_last_error(void);
 
@@ -566,6 +592,34 @@ int bahip_attn_bwd_dv(
     const int64_t dv_strides[3],
     float softmax_scale, int causal, int deterministic, int dtype,
     void* stream);
+
+/* ---- FP8 e4m3 forward (see "FP8" above) -----------------------------------
+ * The GQA argument lists with the three per-tensor descales and the V^T image
+ * workspace.  BAHIP_F8_P_SCALE is the power of two the kernel multiplies P by
+ * before it rounds P to e4m3 (attn_fp8.h: BA_FP8_PSCALE). */
+#define BAHIP_F8_P_SCALE 16
+int64_t bahip_attn_fwd_f8_workspace_bytes(int64_t B, int64_t Sk, int64_t Nk,
+                                          int64_t D);
+int bahip_attn_fwd_f8(
+    const void* q, const void* k, const void* v,
+    float* o, float* lse,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3],
+    const int64_t k_strides[3],
+    const int64_t v_strides[3],
+    float softmax_scale, int causal, int dtype,
+    float descale_q, float descale_k, float descale_v,
+    void* workspace, int64_t workspace_bytes, void* stream);
+int bahip_attn_fwd_accum_f8(
+    void* hip_function,
+    const void* q, const void* k, const void* v,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    float* acc, float* m, float* l, const int64_t acc_strides[3],
+    const int64_t ml_strides[2], int carry_in,
+    float descale_q, float descale_k, float descale_v,
+    void* workspace, int64_t workspace_bytes, void* stream);
 
 /* The empty state, "no key seen yet", over [B, S] rows of a carry-in state
  * (acc strided {b,s,h}, m/l strided {b,h}, as in bahip_attn_fwd_accum):
