@@ -46,6 +46,12 @@ runs, at --seq (65536), dense causal and then the same call with
 softcap=30, and reports next to each capped time its ratio to the plain row
 of the same run.  The FLOPs model is the plain one (the tanh is not counted).
 
+ALiBi:
+  python benchmarks/sweep.py --alibi
+runs, at --seq (65536), causal and then full attention, each plain and then
+with alibi_slopes = 2 ** -(8 (h + 1) / N), and reports next to each ALiBi time
+its ratio to the plain row before it.  The FLOPs model is the plain one.
+
 Row fields mirror the reference's results_torch.jsonl semantics.
 """
 
@@ -88,7 +94,7 @@ def timeit(fn, steps, warmup):
 
 
 def bench_burst(args, b, s_global, n, d, causal, striped, opt_bwd, steps, warmup,
-                nk=None, softcap=0.0):
+                nk=None, softcap=0.0, alibi=False):
     from burst_attn_amd import burst_attn_func, burst_attn_func_striped
 
     world = dist.get_world_size()
@@ -103,6 +109,9 @@ def bench_burst(args, b, s_global, n, d, causal, striped, opt_bwd, steps, warmup
     func = burst_attn_func_striped if striped else burst_attn_func
     if softcap:
         func = functools.partial(func, softcap=softcap)
+    if alibi:
+        slopes = 2.0 ** (-8.0 * torch.arange(1, n + 1, dtype=torch.float32) / n)
+        func = functools.partial(func, alibi_slopes=slopes.cuda())
     if args.dtype == "fp8":  # forward leg only: the fp8 kernels have no backward
         descale = tuple(float(t.float().abs().max()) / 448.0 for t in (q, k, v))
         q8, k8, v8 = ((t.float() / x).to(torch.float8_e4m3fn)
@@ -134,6 +143,7 @@ def bench_burst(args, b, s_global, n, d, causal, striped, opt_bwd, steps, warmup
         "b": b, "s": s_global, "n": n, "nk": nk, "d": d,
         "causal": causal, "opt_bwd": opt_bwd, "wsize": world,
         "dtype": args.dtype, **({"softcap": softcap} if softcap else {}),
+        **({"alibi": True} if alibi else {}),
         "fwd_ms": round(t_f * 1e3, 2),
         "fwd_tflops_per_gpu": round(f / t_f / 1e12 / world, 2),
         "fwdbwd_ms": round(t_fb * 1e3, 2),
@@ -464,6 +474,9 @@ def main():
     p.add_argument("--softcap", type=float, action="append", default=None,
                    help="run dense causal at --seq and the same call with "
                         "this softcap; repeatable; replaces --configs")
+    p.add_argument("--alibi", action="store_true",
+                   help="run causal and full attention at --seq, each plain "
+                        "and with alibi_slopes; replaces --configs")
     args = p.parse_args()
     nk = args.heads if args.kv_heads is None else args.kv_heads
     if nk < 1 or args.heads % nk:
@@ -481,7 +494,8 @@ def main():
 
     rows = []
     n, d = args.heads, args.head_dim
-    if args.dtype == "fp8" and (args.window or args.softcap or args.configs
+    if args.dtype == "fp8" and (args.window or args.softcap or args.alibi
+                                or args.configs
                                 not in ("quick", "ring", "batch", "gqa")):
         p.error("--dtype fp8 runs the quick, ring, batch and gqa configs only")
     if args.window:
@@ -512,6 +526,18 @@ def main():
             r["fwdbwd_ratio_to_plain"] = round(
                 r["fwdbwd_ms"] / plain["fwdbwd_ms"], 4)
             rows.append(r)
+    elif args.alibi:
+        if world != 1:
+            p.error("--alibi is a one-GPU measurement")
+        for causal in (True, False):
+            plain = bench_burst(args, 1, args.seq, n, d, causal, False, False,
+                                args.steps, args.warmup, nk)
+            r = bench_burst(args, 1, args.seq, n, d, causal, False, False,
+                            args.steps, args.warmup, nk, alibi=True)
+            r["fwd_ratio_to_plain"] = round(r["fwd_ms"] / plain["fwd_ms"], 4)
+            r["fwdbwd_ratio_to_plain"] = round(
+                r["fwdbwd_ms"] / plain["fwdbwd_ms"], 4)
+            rows += [plain, r]
     elif args.configs == "quick":  # 1-GPU-friendly sweep
         for s in (16384, 32768, 65536):
             for causal in (False, True):

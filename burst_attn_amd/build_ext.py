@@ -20,14 +20,15 @@ DEVICE_SOURCES = ["attn_fwd.hip", "attn_bwd.hip", "probes.hip",
                   "attn_fwd_softcap.hip", "attn_bwd_softcap.hip",
                   "attn_fwd_blk.hip", "attn_bwd_blk.hip",
                   "attn_hd192_fwd.hip", "attn_hd192_bwd.hip",
-                  "attn_fp8_fwd.hip"]
+                  "attn_fp8_fwd.hip",
+                  "attn_fwd_alibi.hip", "attn_bwd_alibi.hip"]
 # Per-source compiler flags.  The head_dim 256 kernels are built without
 # packed fp32 VALU ops (v_pk_mul_f32 and kin): the accumulator rescale is
 # the one place the compiler would form them, and scalar fp32 ops keep the
 # result independent of their operand forms.  So are the soft-capped
 # D = 64/128 kernels, which is why they are instantiated in sources of their
 # own (each includes its parent's kernel templates), and so are the
-# block-sparse ones.  The older sources keep the flags their tuned code was
+# block-sparse and the ALiBi ones.  The older sources keep the flags their tuned code was
 # measured with.
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
@@ -40,6 +41,8 @@ EXTRA_FLAGS = {
     "attn_hd192_fwd.hip": _NO_PK_F32,
     "attn_hd192_bwd.hip": _NO_PK_F32,
     "attn_fp8_fwd.hip": _NO_PK_F32,
+    "attn_fwd_alibi.hip": _NO_PK_F32,
+    "attn_bwd_alibi.hip": _NO_PK_F32,
 }
 # sources a source includes, beyond the headers: rebuilt when those change
 SOURCE_DEPS = {
@@ -47,6 +50,8 @@ SOURCE_DEPS = {
     "attn_bwd_softcap.hip": ["attn_bwd.hip"],
     "attn_fwd_blk.hip": ["attn_fwd.hip"],
     "attn_bwd_blk.hip": ["attn_bwd.hip"],
+    "attn_fwd_alibi.hip": ["attn_fwd.hip"],
+    "attn_bwd_alibi.hip": ["attn_bwd.hip"],
 }
 HOST_SOURCES = ["ext_torch.cpp"]
 

@@ -81,7 +81,9 @@ constexpr int KVBLK = 64;
 // mask stays on the exponent, where the plain kernel has it.  One ba_blk_args
 // = the block form (attn_common.h, blk_support.h): the loop runs over the
 // workgroup's list of kv tiles, a wave computes a tile iff the entry's bit
-// says so, and the element mask is the plain one.
+// says so, and the element mask is the plain one.  One ba_alibi_args = the
+// ALiBi form: the forward's kb * |distance| joins the raw score before the
+// exponent, and dS needs no other change (the bias has no q, k dependence).
 template <typename T, int D, int DQP = 0, typename... SEG>
 __global__ __launch_bounds__(512) void bwd_dq_kernel(
     const T* __restrict__ dout, const T* __restrict__ q,
@@ -100,13 +102,15 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
   constexpr bool HAS_BAND = ba_pack_is<ba_band_args, SEG...>;
   constexpr bool HAS_CAP = ba_pack_is<ba_cap_args, SEG...>;
   constexpr bool HAS_BLK = ba_pack_is<ba_blk_args, SEG...>;
+  constexpr bool HAS_ALIBI = ba_pack_is<ba_alibi_args, SEG...>;
   constexpr bool HAS_SEG =
-      sizeof...(SEG) != 0 && !HAS_BAND && !HAS_CAP && !HAS_BLK;
+      sizeof...(SEG) != 0 && !HAS_BAND && !HAS_CAP && !HAS_BLK && !HAS_ALIBI;
   constexpr bool HAS_MASK = HAS_SEG || HAS_BAND;
   static_assert(!(HAS_MASK || HAS_CAP) || (sizeof...(SEG) == 1 && DQP == 0),
                 "segment ids / band / softcap: the default dq kernel");
   static_assert(!HAS_BLK || (DQP == 0 && KVBLK == BA_BLK_TILE),
                 "block masks: the default dq kernel, tiles of blk_support.h");
+  static_assert(!HAS_ALIBI || DQP == 0, "ALiBi: the default dq kernel");
   ba_cap_args cp = {0.f, 0.f};
   if constexpr (HAS_CAP) cp = ba_cap_of(seg...);
   // band form: the band is the whole mask (the launcher folded causal in)
@@ -175,6 +179,14 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
       (q_row < Sq) ? lse[b * l_sb + n * l_sh + q_row] * BA_LOG2E : 0.f;
   const float dlt =
       (q_row < Sq) ? delta[b * d_sb + n * d_sh + q_row] : 0.f;
+  // ALiBi form: the forward's bias, recomputed (rows of S^T are kv rows)
+  ba_alibi_args al = {nullptr, 0, 0, 0};
+  float al_kb = 0.f, al_step = 0.f;
+  if constexpr (HAS_ALIBI) {
+    al = ba_alibi_of(seg...);
+    al_kb = ba_alibi_kb(al, b, n, scale);
+    al_step = -(float)al.stride;
+  }
 
   f32x16_t dqt[D / 32];
 #pragma unroll
@@ -327,6 +339,9 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
           dpt = MT::mma(vf, gf[DQP ? 0 : s], dpt);
         }
         }
+        if constexpr (HAS_ALIBI)
+          ba_alibi_add(st, ba_alibi_d0(al, q_row, kv0 + kvs * 32 + 4 * hi),
+                       al_step, al_kb);
         // p^T = exp2(S^T*c2 - lse2);  dS^T = p^T*(dP^T - delta)*scale
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -411,7 +426,9 @@ __global__ __launch_bounds__(512) void bwd_dq_kernel(
 // registers), and p = exp2((t + that) * c2cap), dS = p * dP' * (1 - t^2) *
 // scale with dP' = dP - delta from the fold as before.  One ba_blk_args = the
 // block form: the flattened stream walks the workgroup's list of q tiles once
-// per group member, wrapping to the list's head for the next member.
+// per group member, wrapping to the list's head for the next member.  One
+// ba_alibi_args = the ALiBi form: kb * |distance| joins the folded score, with
+// the slope of the group member being streamed, not one per KV head.
 template <typename T, int D, int MODE, int QBLK = 64, int GQA = 0,
           typename... SEG>
 __global__ __launch_bounds__(512) void bwd_dkv_kernel(
@@ -431,12 +448,22 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
   constexpr bool HAS_BAND = ba_pack_is<ba_band_args, SEG...>;
   constexpr bool HAS_CAP = ba_pack_is<ba_cap_args, SEG...>;
   constexpr bool HAS_BLK = ba_pack_is<ba_blk_args, SEG...>;
+  constexpr bool HAS_ALIBI = ba_pack_is<ba_alibi_args, SEG...>;
   constexpr bool HAS_SEG =
-      sizeof...(SEG) != 0 && !HAS_BAND && !HAS_CAP && !HAS_BLK;
+      sizeof...(SEG) != 0 && !HAS_BAND && !HAS_CAP && !HAS_BLK && !HAS_ALIBI;
   constexpr bool HAS_MASK = HAS_SEG || HAS_BAND;
   static_assert(!HAS_CAP || QBLK == 64, "softcap: the default q tile");
   static_assert(!HAS_BLK || QBLK == BA_BLK_TILE,
                 "block masks: q tiles of blk_support.h");
+  static_assert(!HAS_ALIBI || QBLK == 64, "ALiBi: the default q tile");
+  // ALiBi form: rows of S are q rows here, so the distance grows by +stride
+  // per row; the slope is the QUERY head's and is fetched per group member
+  ba_alibi_args al = {nullptr, 0, 0, 0};
+  float al_step = 0.f;
+  if constexpr (HAS_ALIBI) {
+    al = ba_alibi_of(seg...);
+    al_step = (float)al.stride;
+  }
   ba_cap_args cp = {0.f, 0.f};
   if constexpr (HAS_CAP) cp = ba_cap_of(seg...);
   static_assert(!HAS_MASK || (sizeof...(SEG) == 1 && QBLK == BA_SEG_TILE &&
@@ -631,6 +658,10 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
   for (int t = t0; t < nt; ++t) {
     const int q0 = (HAS_BLK ? (int)(e_cur & BA_BLK_TILE_MASK) : t) * QBLK;
     const bool last_t = (t + 1) >= nt;
+    // ALiBi form: query head n0 + g's factor (a scalar load per tile: g is
+    // workgroup-uniform, and no register has to carry it across the stream)
+    float al_kb = 0.f;
+    if constexpr (HAS_ALIBI) al_kb = ba_alibi_kb(al, b, n0 + g, scale);
     const bool has_next = !last_t || (GQA && g + 1 < ng);
     u32x4_t qreg[PT], greg[PT];
     float2 l2n[QBLK / 32] = {};
@@ -710,6 +741,10 @@ __global__ __launch_bounds__(512) void bwd_dkv_kernel(
             dpt = MT::mma(gfr, vf[s], dpt);
           }
         }
+        // (st holds raw - lse2 / c2 from the fold: the bias adds to either)
+        if constexpr (HAS_ALIBI)
+          ba_alibi_add(st, ba_alibi_d0(al, q0 + qs * 32 + 4 * hi, kv_col),
+                       al_step, al_kb);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int q_loc = qs * 32 + ba_crow(r, 0) + 4 * hi;
@@ -1355,7 +1390,8 @@ static int bwd_entry(
     const int64_t dqs[3], const int64_t dks[3], const int64_t dvs[3],
     float scale, int causal, int deterministic, int dtype, void* stream,
     const bwd_seg_call* seg, const bwd_band_call* band = nullptr,
-    float softcap = 0.f, const ba_blk_call* blk = nullptr) {
+    float softcap = 0.f, const ba_blk_call* blk = nullptr,
+    const ba_alibi_call* alibi = nullptr) {
   (void)deterministic;  // only atomic6 is not deterministic by construction
   if (causal && Sq != Sk)
     return ba_fail(BAHIP_ERR_CAUSAL_SHAPE,
@@ -1385,6 +1421,18 @@ static int bwd_entry(
                      "%s=%d does not support softcap (default backward plan "
                      "only)",
                      sv.knob, sv.value);
+  }
+  if (alibi) {
+    // the ALiBi kernels exist for the default plan only, at D = 64 and 128
+    const ba_seg_verdict sv = ba_seg_bwd_support(kn);
+    if (sv.knob)
+      return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                     "%s=%d does not support ALiBi (default backward plan "
+                     "only)",
+                     sv.knob, sv.value);
+    if (D == BA_D256)
+      return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                     "head_dim 256 does not support ALiBi (plain calls only)");
   }
   if (plan.verdict == BA_BWD_NO_GQA)
     return ba_fail(BAHIP_ERR_UNSUPPORTED,
@@ -1523,6 +1571,17 @@ static int bwd_entry(
     return ba_cap_bwd(dqa, dva, dka, ba_cap_for(scale, softcap), B, D, dtype,
                       (hipStream_t)stream);
   }
+  if (alibi) {
+    // the default plan's kernels in their ALiBi form (attn_bwd_alibi.hip); the
+    // knobs and head_dim 256 were refused above
+    if (B < 1 || B > 65535 || Sq < 1 || Sk < 1)
+      return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                     "ALiBi: unsupported shape B=%d Sq=%d Sk=%d", (int)B,
+                     (int)Sq, (int)Sk);
+    const ba_alibi_args al = {alibi->slopes, alibi->batch_stride,
+                              (int32_t)alibi->offset, (int32_t)alibi->stride};
+    return ba_alibi_bwd(dqa, dva, dka, al, B, D, dtype, (hipStream_t)stream);
+  }
   const bwd_dkq_args dkqa = {
       dout, q, k, v, delta, lse, dq, dk, dv, iSq, iSk, iN,
       gs[0], gs[1], gs[2], qs[0], qs[1], qs[2], ks[0], ks[1], ks[2],
@@ -1618,6 +1677,29 @@ extern "C" int bahip_attn_bwd_softcap(
   return bwd_entry(dout, q, k, v, delta, lse, dq, dk, dv, B, Sq, Sk, N, Nk, D,
                    gs, qs, ks, vs, ds, ls, dqs, dks, dvs, scale, causal,
                    deterministic, dtype, stream, nullptr, nullptr, softcap);
+}
+
+extern "C" int bahip_attn_bwd_alibi(
+    const void* dout, const void* q, const void* k, const void* v,
+    const float* delta, const float* lse, float* dq, float* dk, float* dv,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t gs[3], const int64_t qs[3], const int64_t ks[3],
+    const int64_t vs[3], const int64_t ds[2], const int64_t ls[2],
+    const int64_t dqs[3], const int64_t dks[3], const int64_t dvs[3],
+    float scale, int causal, int deterministic, int dtype, const float* slopes,
+    int64_t slopes_batch_stride, int64_t pos_offset, int64_t pos_stride,
+    void* stream) {
+  if (slopes && !ba_alibi_valid(pos_offset, pos_stride, Sq, Sk))
+    return ba_fail(BAHIP_ERR_ALIBI,
+                   "ALiBi: pos_stride=%lld must be >= 1 and |pos_offset=%lld| "
+                   "+ pos_stride * max(Sq, Sk) at most 2^30",
+                   (long long)pos_stride, (long long)pos_offset);
+  const ba_alibi_call ac = {slopes, slopes_batch_stride, pos_offset,
+                            pos_stride};
+  return bwd_entry(dout, q, k, v, delta, lse, dq, dk, dv, B, Sq, Sk, N, Nk, D,
+                   gs, qs, ks, vs, ds, ls, dqs, dks, dvs, scale, causal,
+                   deterministic, dtype, stream, nullptr, nullptr, 0.f,
+                   nullptr, slopes ? &ac : nullptr);
 }
 
 extern "C" int bahip_attn_bwd_blk(

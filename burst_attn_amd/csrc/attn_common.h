@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "alibi_support.h"
 #include "band_support.h"
 #include "blk_support.h"
 #include "cap_support.h"
@@ -193,6 +194,43 @@ __device__ __forceinline__ float ba_cap_tanh(float s, float a) {
   return __builtin_fmaf(-2.f, __builtin_amdgcn_rcpf(1.f + ba_exp2(s * a)), 1.f);
 }
 
+// ---- ALiBi ----------------------------------------------------------------
+// The ALiBi form of a kernel takes one ba_alibi_args (alibi_support.h) in the
+// same trailing pack: every raw score gets kb * |d| added, d the signed
+// position distance of its pair, and nothing masks but the kernel's own range
+// and causal rule.  The bias is never a table: a lane derives the distance of
+// its first accumulator element once per 32x32 subtile (ba_alibi_d0) and the
+// other 15 follow by compile-time multiples of the stride (ba_alibi_add), so a
+// score costs two FMAs, the second with the |.| source modifier.
+__device__ __forceinline__ ba_alibi_args ba_alibi_of(const ba_alibi_args& a) {
+  return a;
+}
+// kb = -slope / softmax_scale of (batch b, query head h): a workgroup-uniform
+// index, so the read is one scalar load (the slopes are only read)
+__device__ __forceinline__ float ba_alibi_kb(const ba_alibi_args& a, int b,
+                                             int h, float scale) {
+  typedef const __attribute__((address_space(4))) float* cptr;
+  return -((cptr)(uintptr_t)a.slopes)[(int64_t)b * a.batch_stride + h] / scale;
+}
+// stride * (i - j) + offset as a float.  Wrapping arithmetic: rows a tile pads
+// past the tensors may leave the checked range, and their scores are masked.
+__device__ __forceinline__ float ba_alibi_d0(const ba_alibi_args& a, int i,
+                                             int j) {
+  return (float)(int)((uint32_t)a.stride * (uint32_t)(i - j) +
+                      (uint32_t)a.offset);
+}
+// s[r] += kb * |d0 + step * ba_crow(r, 0)|: `step` is -stride where the
+// accumulator's rows are kv rows (S^T, forward and dq), +stride where they are
+// q rows (dK/dV)
+__device__ __forceinline__ void ba_alibi_add(f32x16_t& s, float d0, float step,
+                                             float kb) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+    s[r] = __builtin_fmaf(
+        __builtin_fabsf(__builtin_fmaf((float)ba_crow(r, 0), step, d0)), kb,
+        s[r]);
+}
+
 // ---- block masks (block-sparse attention) --------------------------------
 // The block form of a kernel takes one ba_blk_args in the same trailing pack:
 // the workgroup's tile loop runs over a LIST of streamed tiles instead of a
@@ -200,7 +238,7 @@ __device__ __forceinline__ float ba_cap_tanh(float s, float a) {
 // entry naming the waves that compute the tile.  A listed tile is wholly
 // block-visible to those waves, so the only element masks are the plain
 // kernel's own (range tail, causal).  So a pack holds nothing (plain), or one
-// of ba_seg_args, ba_band_args, ba_cap_args, ba_blk_args.
+// of ba_seg_args, ba_band_args, ba_cap_args, ba_alibi_args, ba_blk_args.
 struct ba_blk_args {
   const uint32_t* list;  // [Bm][Hm][gridDim.x][stride] entries
   const int32_t* cnt;    // [Bm][Hm][gridDim.x] entries of each list

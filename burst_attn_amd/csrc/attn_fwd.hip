@@ -119,7 +119,12 @@ __device__ __forceinline__ int ba_buf_of(ba_dyn d) { return d.value; }
 // list[t] computes; a wave computes a tile iff the entry's bit says so; such a
 // tile is `full` by the plain rule and masked by the plain rule; no exp sees a
 // masked entry at the empty level, so there is no select.
-// Default variant with VSRC=0 only.
+// Default variant with VSRC=0 only.  One ba_alibi_args = the ALiBi form
+// (attn_common.h, alibi_support.h): kb * |distance| joins every raw score
+// before the subtile's max, in raw units, so the max, the exp2, the masks and
+// the state contract are the plain kernel's (the running max is then one of
+// biased scores, which is what rounds must merge).  Default variant with
+// VSRC=0 only.
 template <typename T, int D, int KVBLK, int OUT_STATE, int VPATH, int SUBT,
           int NT = 512, int NBUF = 2, int KREG = 0, int VSRC = 0,
           typename... SEG>
@@ -141,11 +146,15 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
   constexpr bool HAS_BAND = ba_pack_is<ba_band_args, SEG...>;
   constexpr bool HAS_CAP = ba_pack_is<ba_cap_args, SEG...>;
   constexpr bool HAS_BLK = ba_pack_is<ba_blk_args, SEG...>;
+  constexpr bool HAS_ALIBI = ba_pack_is<ba_alibi_args, SEG...>;
   constexpr bool HAS_SEG =
-      sizeof...(SEG) != 0 && !HAS_BAND && !HAS_CAP && !HAS_BLK;
+      sizeof...(SEG) != 0 && !HAS_BAND && !HAS_CAP && !HAS_BLK && !HAS_ALIBI;
   // either form: entries can be masked inside the tensors' ranges, so a row
   // may see no key (weight-0 select, l = 0 epilogue)
   constexpr bool HAS_MASK = HAS_SEG || HAS_BAND;
+  static_assert(!HAS_ALIBI || (VPATH == 0 && SUBT == 1 && NT == 512 &&
+                               NBUF == 2 && KREG == 0 && VSRC == 0),
+                "ALiBi: the default variant, V transposed in-kernel");
   static_assert(!HAS_BLK || (VPATH == 0 && SUBT == 1 && NT == 512 &&
                              NBUF == 2 && KREG == 0 && VSRC == 0 &&
                              KVBLK == BA_BLK_TILE && NT / 2 == BA_BLK_BLOCK),
@@ -356,6 +365,15 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
   ba_cap_args cp = {0.f, 0.f};
   bool cap_masked = false;
   if constexpr (HAS_CAP) cp = ba_cap_of(seg...);
+  // ALiBi form: the head's bias factor in raw-score units (one scalar load
+  // per workgroup) and -stride as a float (the accumulator's rows are kv rows)
+  ba_alibi_args al = {nullptr, 0, 0, 0};
+  float al_kb = 0.f, al_step = 0.f;
+  if constexpr (HAS_ALIBI) {
+    al = ba_alibi_of(seg...);
+    al_kb = ba_alibi_kb(al, b, n, scale);
+    al_step = -(float)al.stride;
+  }
   static_assert(SUBT != 2 || (NBUF == 4 && VPATH == 0),
                 "the T15 pipeline needs NBUF=4 and the V^T image");
   static_assert(SUBT != 3 || (NBUF == 4 && VPATH == 0 && NT == 256),
@@ -798,6 +816,11 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(
           // (tile t+1's buffer was staged two tiles ago, ordered by the
           // per-tile barrier)
           if (KREG == 2) load_next_kfrags(t, kvs, kres);
+          // ALiBi form: the bias joins the raw scores before the max; the
+          // masks come after it and everything below is the plain kernel's
+          if constexpr (HAS_ALIBI)
+            ba_alibi_add(st, ba_alibi_d0(al, q_row, kv0 + kvs * 32 + 4 * hi),
+                         al_step, al_kb);
           if (!full) mask_sub(st, kv0, kvs * 32);
           if constexpr (HAS_CAP) cap_masked = !full;
           frag pf[2];
@@ -1367,6 +1390,42 @@ static int fwd_cap_entry(const fwd_args& a, float softcap, int out_state,
                     stream);
 }
 
+// ---- ALiBi form -------------------------------------------------------------
+// What a *_alibi entry point adds to the plain call; null slopes = that call.
+static int ba_alibi_given(const float* slopes, int64_t batch_stride,
+                          int64_t offset, int64_t stride, int64_t Sq,
+                          int64_t Sk, ba_alibi_call* out, bool* given) {
+  *given = slopes != nullptr;
+  if (!*given) return 0;
+  if (!ba_alibi_valid(offset, stride, Sq, Sk))
+    return ba_fail(BAHIP_ERR_ALIBI,
+                   "ALiBi: pos_stride=%lld must be >= 1 and |pos_offset=%lld| "
+                   "+ pos_stride * max(Sq, Sk) at most 2^30",
+                   (long long)stride, (long long)offset);
+  *out = {slopes, batch_stride, offset, stride};
+  return 0;
+}
+
+// The forward with slopes: as with ids, bands and caps, the default variant
+// only, V transposed in the kernel (the V^T workspace is ignored), never the
+// module kernel.  The kernels are attn_fwd_alibi.hip's.
+static int fwd_alibi_entry(const fwd_args& a, const ba_alibi_call& ac,
+                           void* hip_function, int out_state, int64_t B,
+                           int64_t Sq, int64_t Sk, int64_t D, int dtype,
+                           hipStream_t stream) {
+  if (hip_function)
+    return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                   "a module-launched forward does not support ALiBi");
+  if (int rc = fwd_default_variant_only("ALiBi")) return rc;
+  if (B < 1 || B > 65535 || Sq < 1 || Sk < 1)
+    return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                   "ALiBi: unsupported shape B=%d Sq=%d Sk=%d", (int)B,
+                   (int)Sq, (int)Sk);
+  const ba_alibi_args al = {ac.slopes, ac.batch_stride, (int32_t)ac.offset,
+                            (int32_t)ac.stride};
+  return ba_alibi_fwd(a, al, out_state, B, D, dtype, stream);
+}
+
 // The per-call knobs: the variant the BA_FWD_* table selects, and whether
 // a call with these shapes stages V from the V^T image (vt_image.h).
 // BA_FWD_VT=1 forces the image wherever the default variant runs, 0 forces
@@ -1436,7 +1495,8 @@ static int fwd_entry(void* hip_function, int out_state, const void* q,
                      int carry_in, void* ws, int64_t ws_bytes, void* stream,
                      const fwd_seg_call* seg = nullptr,
                      const fwd_band_call* band = nullptr,
-                     float softcap = 0.f, const ba_blk_call* blk = nullptr) {
+                     float softcap = 0.f, const ba_blk_call* blk = nullptr,
+                     const ba_alibi_call* alibi = nullptr) {
   if (causal && Sq != Sk)
     return ba_fail(BAHIP_ERR_CAUSAL_SHAPE,
                    "causal tiles require Sq == Sk (%d vs %d)", (int)Sq,
@@ -1459,6 +1519,7 @@ static int fwd_entry(void* hip_function, int out_state, const void* q,
     const char* what = seg            ? "segment ids"
                        : band         ? "a band"
                        : blk          ? "a block mask"
+                       : alibi        ? "ALiBi"
                        : hip_function ? "a module-launched forward"
                                       : nullptr;
     if (what)
@@ -1486,6 +1547,9 @@ static int fwd_entry(void* hip_function, int out_state, const void* q,
   if (softcap > 0.f)
     return fwd_cap_entry(a, softcap, out_state, B, Sq, Sk, D, dtype,
                          (hipStream_t)stream);
+  if (alibi)
+    return fwd_alibi_entry(a, *alibi, hip_function, out_state, B, Sq, Sk, D,
+                           dtype, (hipStream_t)stream);
   if (blk) {
     // The forward with a block mask: as with ids and bands, the default
     // variant only, V transposed in the kernel (the V^T workspace is
@@ -1691,6 +1755,45 @@ extern "C" int bahip_attn_fwd_accum_softcap(
                    causal, dtype, acc, m, l, acc_strides, ml_strides, carry_in,
                    workspace, workspace_bytes, stream, nullptr, nullptr,
                    capped ? softcap : 0.f);
+}
+
+extern "C" int bahip_attn_fwd_alibi(
+    const void* q, const void* k, const void* v, float* o, float* lse,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    const float* slopes, int64_t slopes_batch_stride, int64_t pos_offset,
+    int64_t pos_stride, void* stream) {
+  ba_alibi_call ac;
+  bool given;
+  if (int rc = ba_alibi_given(slopes, slopes_batch_stride, pos_offset,
+                              pos_stride, Sq, Sk, &ac, &given))
+    return rc;
+  return fwd_entry(nullptr, 0, q, k, v, o, lse, B, Sq, Sk, N, Nk, D, q_strides,
+                   k_strides, v_strides, softmax_scale, causal, dtype, nullptr,
+                   nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, stream,
+                   nullptr, nullptr, 0.f, nullptr, given ? &ac : nullptr);
+}
+
+extern "C" int bahip_attn_fwd_accum_alibi(
+    void* hip_function, const void* q, const void* k, const void* v,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    float* acc, float* m, float* l, const int64_t acc_strides[3],
+    const int64_t ml_strides[2], int carry_in, const float* slopes,
+    int64_t slopes_batch_stride, int64_t pos_offset, int64_t pos_stride,
+    void* stream) {
+  ba_alibi_call ac;
+  bool given;
+  if (int rc = ba_alibi_given(slopes, slopes_batch_stride, pos_offset,
+                              pos_stride, Sq, Sk, &ac, &given))
+    return rc;
+  return fwd_entry(hip_function, 1, q, k, v, nullptr, nullptr, B, Sq, Sk, N,
+                   Nk, D, q_strides, k_strides, v_strides, softmax_scale,
+                   causal, dtype, acc, m, l, acc_strides, ml_strides, carry_in,
+                   nullptr, 0, stream, nullptr, nullptr, 0.f, nullptr,
+                   given ? &ac : nullptr);
 }
 
 extern "C" int bahip_attn_fwd_blk(

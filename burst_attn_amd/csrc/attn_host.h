@@ -9,6 +9,7 @@
 #include <stdlib.h>
 
 #include "../../include/burst_attn_hip.h"
+#include "alibi_support.h"
 #include "blk_support.h"
 #include "cap_support.h"
 
@@ -114,6 +115,21 @@ int ba_cap_fwd(const fwd_args& a, const ba_cap_args& cp, int out_state,
 int ba_cap_bwd(const bwd_dq_args& dq, const bwd_dq_args& dv,
                const bwd_dq_args& dk, const ba_cap_args& cp, int64_t B,
                int64_t D, int dtype, hipStream_t stream);
+
+// ALiBi form of the D = 64/128 kernels (alibi_support.h): what a *_alibi entry
+// point adds to the plain call, and the launches of the default forward
+// variant and the default backward plan's three kernels (attn_fwd_alibi.hip /
+// attn_bwd_alibi.hip, built without packed fp32 VALU ops).  The callers have
+// validated shapes, heads, knobs and the position range.
+struct ba_alibi_call {
+  const float* slopes;
+  int64_t batch_stride, offset, stride;
+};
+int ba_alibi_fwd(const fwd_args& a, const ba_alibi_args& al, int out_state,
+                 int64_t B, int64_t D, int dtype, hipStream_t stream);
+int ba_alibi_bwd(const bwd_dq_args& dq, const bwd_dq_args& dv,
+                 const bwd_dq_args& dk, const ba_alibi_args& al, int64_t B,
+                 int64_t D, int dtype, hipStream_t stream);
 
 // Block form of the D = 64/128 kernels (blk_support.h): what a *_blk entry
 // point adds to the plain call, its validation, the pre-pass and the launches

@@ -285,6 +285,49 @@ at::Tensor attn_seg_prepass(const at::Tensor& q_seg, const at::Tensor& kv_seg) {
   return ws;
 }
 
+// ALiBi slopes of a call: fp32 [N] or [1 or B, N] on q's device, one per
+// query head, with the position offset and stride of the two tensors
+// (include/burst_attn_hip.h).  Never together with ids, a band, a cap, a block
+// mask, fp8 inputs or unequal widths (those combinations have no kernel form
+// yet); the range of the positions is the launcher's to refuse.
+struct Alibi {
+  const float* slopes = nullptr;
+  int64_t batch_stride = 0;
+  at::Tensor t;  // keeps a contiguous copy alive
+};
+
+Alibi alibi_given(const c10::optional<at::Tensor>& slopes, const at::Tensor& q,
+                  const at::Tensor& v, const SegIds& seg, bool band,
+                  double softcap, bool block_mask, bool descale) {
+  Alibi a;
+  if (!slopes.has_value()) return a;
+  const char* what = seg.q            ? "q_seg/kv_seg"
+                     : band           ? "band_lo/band_hi"
+                     : softcap != 0.0 ? "softcap"
+                     : block_mask     ? "block_mask"
+                     : (is_fp8(q) || descale)
+                         ? "fp8 (float8_e4m3fn) inputs"
+                         : nullptr;
+  TORCH_CHECK(!what, "alibi_slopes and ", what,
+              " are not supported together yet");
+  TORCH_CHECK(v.size(3) == q.size(3), "head_dim pair (", q.size(3), ", ",
+              v.size(3), ") does not support alibi_slopes (plain calls only)");
+  const at::Tensor& t = *slopes;
+  TORCH_CHECK(t.scalar_type() == at::kFloat, "alibi_slopes must be fp32, got ",
+              t.scalar_type());
+  TORCH_CHECK(t.device() == q.device(), "alibi_slopes must be on q's device");
+  const int64_t B = q.size(0), N = q.size(2);
+  TORCH_CHECK((t.dim() == 1 && t.size(0) == N) ||
+                  (t.dim() == 2 && (t.size(0) == 1 || t.size(0) == B) &&
+                   t.size(1) == N),
+              "alibi_slopes must be [N] or [1 or B, N] = [", B, ", ", N,
+              "], got ", t.sizes());
+  a.t = t.contiguous();
+  a.slopes = a.t.data_ptr<float>();
+  a.batch_stride = (a.t.dim() == 2 && a.t.size(0) == B && B > 1) ? N : 0;
+  return a;
+}
+
 // Unequal q/k and v widths have the plain kernel form only.
 void check_plain_dv(int64_t D, int64_t Dv, const SegIds& seg, bool band,
                     bool capped, const BlkMask& blk) {
@@ -308,10 +351,28 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k,
                                  const c10::optional<at::Tensor>& block_mask,
                                  int64_t block_size,
                                  const c10::optional<at::Tensor>& blk_ws,
-                                 const Descale& descale) {
+                                 const Descale& descale,
+                                 const c10::optional<at::Tensor>& alibi_slopes,
+                                 int64_t alibi_offset, int64_t alibi_stride) {
   check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
+  if (alibi_slopes.has_value()) {
+    const SegIds seg = seg_ids(q_seg, kv_seg, q, k);
+    const Alibi al = alibi_given(
+        alibi_slopes, q, v, seg, band_given(band_lo, band_hi, seg), softcap,
+        block_mask.has_value(), descale.has_value());
+    auto o = at::empty({B, Sq, N, D}, q.options().dtype(at::kFloat));
+    auto lse = at::empty({B, N, Sq}, q.options().dtype(at::kFloat));
+    // the ALiBi forward transposes V in the kernel: no image workspace
+    BA_CALL(bahip_attn_fwd_alibi(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr<float>(),
+        lse.data_ptr<float>(), B, Sq, Sk, N, k.size(2), D, Strides3(q),
+        Strides3(k), Strides3(v), (float)softmax_scale, causal ? 1 : 0,
+        dtype_code(q), al.slopes, al.batch_stride, alibi_offset, alibi_stride,
+        at::hip::getCurrentHIPStream().stream()));
+    return {o, lse};
+  }
   if (is_fp8(q)) {
     check_fp8_plain(q_seg, kv_seg, band_lo, band_hi, softcap, block_mask);
     check_fp8_widths(q, v);
@@ -436,7 +497,10 @@ void fwd_accum_call(void* asm_fn, const at::Tensor& q, const at::Tensor& k,
                     const c10::optional<at::Tensor>& block_mask = c10::nullopt,
                     int64_t block_size = 64,
                     const c10::optional<at::Tensor>& blk_ws = c10::nullopt,
-                    const Descale& descale = c10::nullopt) {
+                    const Descale& descale = c10::nullopt,
+                    const c10::optional<at::Tensor>& alibi_slopes =
+                        c10::nullopt,
+                    int64_t alibi_offset = 0, int64_t alibi_stride = 1) {
   check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
@@ -459,6 +523,19 @@ void fwd_accum_call(void* asm_fn, const at::Tensor& q, const at::Tensor& k,
   int64_t mls[2] = {m.stride(0), m.stride(1)};
   TORCH_CHECK(l.stride(0) == mls[0] && l.stride(1) == mls[1],
               "m/l stride mismatch");
+  if (alibi_slopes.has_value()) {
+    const Alibi al = alibi_given(
+        alibi_slopes, q, v, seg, band_given(band_lo, band_hi, seg), softcap,
+        block_mask.has_value(), descale.has_value());
+    BA_CALL(bahip_attn_fwd_accum_alibi(
+        asm_fn, q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Sq, Sk, N,
+        k.size(2), D, Strides3(q), Strides3(k), Strides3(v),
+        (float)softmax_scale, causal ? 1 : 0, dtype_code(q),
+        acc.data_ptr<float>(), m.data_ptr<float>(), l.data_ptr<float>(),
+        Strides3(acc), mls, carry_in ? 1 : 0, al.slopes, al.batch_stride,
+        alibi_offset, alibi_stride, at::hip::getCurrentHIPStream().stream()));
+    return;
+  }
   if (is_fp8(q)) {
     const auto [dq, dk, dv] = descale.value_or(std::make_tuple(1.0, 1.0, 1.0));
     auto ws = fp8_workspace(k);
@@ -540,10 +617,13 @@ void attn_fwd_accum(const at::Tensor& q, const at::Tensor& k,
                     const c10::optional<at::Tensor>& block_mask,
                     int64_t block_size,
                     const c10::optional<at::Tensor>& blk_ws,
-                    const Descale& descale) {
+                    const Descale& descale,
+                    const c10::optional<at::Tensor>& alibi_slopes,
+                    int64_t alibi_offset, int64_t alibi_stride) {
   fwd_accum_call(nullptr, q, k, v, softmax_scale, causal, acc, m, l, carry_in,
                  q_seg, kv_seg, band_lo, band_hi, softcap, block_mask,
-                 block_size, blk_ws, descale);
+                 block_size, blk_ws, descale, alibi_slopes, alibi_offset,
+                 alibi_stride);
 }
 
 // The empty carry-in state ("no key seen yet") written into acc [B,S,N,D],
@@ -630,7 +710,9 @@ void attn_bwd_accum(const at::Tensor& dout, const at::Tensor& q,
                     const c10::optional<int64_t>& band_hi, double softcap,
                     const c10::optional<at::Tensor>& block_mask,
                     int64_t block_size,
-                    const c10::optional<at::Tensor>& blk_ws) {
+                    const c10::optional<at::Tensor>& blk_ws,
+                    const c10::optional<at::Tensor>& alibi_slopes,
+                    int64_t alibi_offset, int64_t alibi_stride) {
   check_no_fp8_bwd(q);
   check_qkv(dout, "dout");
   check_qkv3(q, k, v);
@@ -655,6 +737,19 @@ void attn_bwd_accum(const at::Tensor& dout, const at::Tensor& q,
   int64_t ls[2] = {lse.stride(0), lse.stride(1)};
   auto stream = at::hip::getCurrentHIPStream().stream();
   const bool band = band_given(band_lo, band_hi, seg);
+  if (alibi_slopes.has_value()) {
+    const Alibi al = alibi_given(alibi_slopes, q, v, seg, band, softcap,
+                                 block_mask.has_value(), false);
+    BA_CALL(bahip_attn_bwd_alibi(
+        dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+        delta.data_ptr<float>(), lse.data_ptr<float>(), dq.data_ptr<float>(),
+        dk.data_ptr<float>(), dv.data_ptr<float>(), B, Sq, Sk, N, k.size(2), D,
+        Strides3(dout), Strides3(q), Strides3(k), Strides3(v), ds, ls,
+        Strides3(dq), Strides3(dk), Strides3(dv), (float)softmax_scale,
+        causal ? 1 : 0, deterministic ? 1 : 0, dtype_code(q), al.slopes,
+        al.batch_stride, alibi_offset, alibi_stride, stream));
+    return;
+  }
   const BlkMask blk = blk_mask(block_mask, block_size, blk_ws, q, Sq, Sk, seg,
                                band, softcap);
   if (v.size(3) != D) {
@@ -723,7 +818,9 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
                                  double softcap,
                                  const c10::optional<at::Tensor>& block_mask,
                                  int64_t block_size,
-                                 const c10::optional<at::Tensor>& blk_ws) {
+                                 const c10::optional<at::Tensor>& blk_ws,
+                                 const c10::optional<at::Tensor>& alibi_slopes,
+                                 int64_t alibi_offset, int64_t alibi_stride) {
   check_no_fp8_bwd(q);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
@@ -735,7 +832,8 @@ std::vector<at::Tensor> attn_bwd(const at::Tensor& dout, const at::Tensor& q,
   auto dv = at::zeros({B, Sk, Nk, v.size(3)}, q.options().dtype(at::kFloat));
   attn_bwd_accum(dout, q, k, v, delta, lse, softmax_scale, causal,
                  deterministic, dq, dk, dv, q_seg, kv_seg, band_lo, band_hi,
-                 softcap, block_mask, block_size, blk_ws);
+                 softcap, block_mask, block_size, blk_ws, alibi_slopes,
+                 alibi_offset, alibi_stride);
   return {dq, dk, dv};
 }
 
@@ -818,7 +916,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("kv_seg") = py::none(), py::arg("band_lo") = py::none(),
         py::arg("band_hi") = py::none(), py::arg("softcap") = 0.0,
         py::arg("block_mask") = py::none(), py::arg("block_size") = 64,
-        py::arg("blk_ws") = py::none(), py::arg("descale") = py::none());
+        py::arg("blk_ws") = py::none(), py::arg("descale") = py::none(),
+        py::arg("alibi_slopes") = py::none(), py::arg("alibi_offset") = 0,
+        py::arg("alibi_stride") = 1);
   m.def("attn_fwd_accum", &attn_fwd_accum,
         "carry-in accumulator fwd tile (in-kernel LSE merge)", py::arg("q"),
         py::arg("k"), py::arg("v"), py::arg("softmax_scale"),
@@ -827,7 +927,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("kv_seg") = py::none(), py::arg("band_lo") = py::none(),
         py::arg("band_hi") = py::none(), py::arg("softcap") = 0.0,
         py::arg("block_mask") = py::none(), py::arg("block_size") = 64,
-        py::arg("blk_ws") = py::none(), py::arg("descale") = py::none());
+        py::arg("blk_ws") = py::none(), py::arg("descale") = py::none(),
+        py::arg("alibi_slopes") = py::none(), py::arg("alibi_offset") = 0,
+        py::arg("alibi_stride") = 1);
   m.def("attn_fp8_p_scale", [] { return (double)BAHIP_F8_P_SCALE; },
         "the power of two the fp8 forward multiplies P by before it rounds "
         "P to e4m3");
@@ -863,7 +965,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("band_lo") = py::none(), py::arg("band_hi") = py::none(),
         py::arg("softcap") = 0.0,
         py::arg("block_mask") = py::none(), py::arg("block_size") = 64,
-        py::arg("blk_ws") = py::none());
+        py::arg("blk_ws") = py::none(),
+        py::arg("alibi_slopes") = py::none(), py::arg("alibi_offset") = 0,
+        py::arg("alibi_stride") = 1);
   m.def("attn_bwd_accum", &attn_bwd_accum,
         "bwd tile accumulating into fp32 dq/dk/dv views", py::arg("dout"),
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("delta"),
@@ -873,7 +977,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("band_lo") = py::none(), py::arg("band_hi") = py::none(),
         py::arg("softcap") = 0.0,
         py::arg("block_mask") = py::none(), py::arg("block_size") = 64,
-        py::arg("blk_ws") = py::none());
+        py::arg("blk_ws") = py::none(),
+        py::arg("alibi_slopes") = py::none(), py::arg("alibi_offset") = 0,
+        py::arg("alibi_stride") = 1);
   m.def("mfma_probe", &mfma_probe, "32x32x16 MFMA layout probe");
   m.def("fp8_mfma_probe", &fp8_mfma_probe, "32x32x64 fp8 MFMA layout probe");
   m.def("tr16_probe", &tr16_probe, "ds_read_tr16_b64 semantics probe");

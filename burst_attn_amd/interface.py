@@ -86,6 +86,20 @@ round hands the tile provider ``descale=``.  Inputs that require grad,
 and a malformed ``descale`` are refused before any round, and so is
 ``descale`` with 16-bit inputs, whose calls are otherwise unchanged.
 
+ALiBi: the trailing keyword ``alibi_slopes`` (the flash-attn convention: an
+fp32 tensor ``[N]`` or ``[B, N]`` on q's device, one slope per *query* head)
+adds ``-slope[b, h] * |i - j|`` to the score of the query at GLOBAL position i
+and the key at global position j, before the softmax and before ``causal``.
+The global positions follow the op's data layout as a window's do
+(``_window_layout``); ``alibi_tiles`` turns a round into one tile call per (q
+piece, kv piece) pair, each with ``alibi=(slopes, offset, stride)`` so that
+``stride * (i_local - j_local) + offset`` is the pair's global distance, merged
+into a state that starts empty.  The slopes are per head and the same on every
+rank: nothing new travels.  They get no gradient, and a tensor that requires
+one is refused.  Without slopes neither the provider calls nor the kernels
+change.  Slopes together with ``segment_ids``, an effective window, a cap, a
+block mask, fp8 inputs, head_dim 256 or the (192, 128) widths are refused.
+
 The two causal load-balancing layouts (see oracle/partition.py) run the
 same code: ``OpBurstAttn`` (zigzag: rank r holds global chunks [r] and
 [2W-1-r]) and ``OpBurstAttnStrip`` (striped: token t on rank t mod W) only
@@ -108,7 +122,7 @@ from .tile import get_tile_provider
 _logger = get_logger(__name__, level="WARN")
 
 __all__ = ["burst_attn_func", "burst_attn_func_striped", "OpBurstAttn",
-           "OpBurstAttnStrip", "window_tiles", "block_tiles"]
+           "OpBurstAttnStrip", "window_tiles", "block_tiles", "alibi_tiles"]
 
 
 def get_partition_id(double_group, r, process_group=None):
@@ -250,6 +264,41 @@ def block_tiles(a, b, W, s_local, causal):
                 continue
             out.append((slice(lq, lq + nq), slice(lk, lk + nk), Pk,
                         causal and Pk == Pq))
+    return out
+
+
+def alibi_tiles(layout, a, b, W, s_local, causal):
+    """The tile calls that one ring round makes of the q chunk owned by rank
+    ``a`` against the kv chunk owned by rank ``b`` with ALiBi: a list of
+    ``(q_rows, kv_rows, offset, stride, tile_causal)``, one per (q piece, kv
+    piece) pair of the two ranks (``_pieces``) that holds a visible pair.  For
+    local rows i of ``q_rows`` and j of ``kv_rows`` (counted from the slices'
+    starts) ``stride * (i - j) + offset`` is the distance of their global
+    positions.  Which pairs are dropped, causal or plain are the decisions of
+    ``tile_window``: unit-stride pieces (zigzag halves, contiguous chunks) are
+    aligned and equally long, so with ``causal`` a later kv piece is dropped,
+    the same piece is a causal call and an earlier one a plain call; a striped
+    pair is the causal tile for ``b <= a`` and the causal tile shifted by one
+    row for ``b > a``, whose shift the offset absorbs."""
+    out = []
+    for lq, nq, Pq, stride in _pieces(layout, a, W, s_local):
+        for lk, nk, Pk, _ in _pieces(layout, b, W, s_local):
+            q0 = k0 = 0
+            tile_causal = False
+            if causal and stride == 1:
+                if Pk > Pq:
+                    continue
+                tile_causal = Pk == Pq
+            elif causal:
+                tile_causal = True
+                if Pk > Pq:  # row i sees columns < i: rows 1.., columns ..-1
+                    q0, nq, nk = 1, nq - 1, nk - 1
+                    if nq < 1:
+                        continue
+            out.append((slice(lq + q0, lq + q0 + nq),
+                        slice(lk + k0, lk + k0 + nk),
+                        (Pq + stride * q0) - (Pk + stride * k0), stride,
+                        tile_causal))
     return out
 
 
@@ -495,6 +544,50 @@ def _check_block_mask(block_mask, block_size, q, k, causal, segment_ids,
     return block_mask.to(torch.uint8).contiguous(), bs
 
 
+def _check_alibi(alibi_slopes, q, k, v, segment_ids, window, softcap,
+                 block_mask):
+    """None, or the slopes as contiguous fp32 ``[1 or B, N]``.  Everything a
+    call with slopes cannot have is refused here, before any round."""
+    t = alibi_slopes
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(
+            f"alibi_slopes must be a tensor, got {type(t).__name__}"
+        )
+    if t.dtype != torch.float32:
+        raise ValueError(f"alibi_slopes must be float32, got {t.dtype}")
+    B, N = q.shape[0], q.shape[2]
+    if tuple(t.shape) not in ((N,), (B, N)):
+        raise ValueError(
+            f"alibi_slopes must be [N] = [{N}] or [B, N] = [{B}, {N}] (one "
+            f"slope per query head), got {tuple(t.shape)}"
+        )
+    if t.device != q.device:
+        raise ValueError(f"alibi_slopes is on {t.device}, q on {q.device}")
+    if t.requires_grad:
+        raise ValueError(
+            "alibi_slopes that require grad are not supported: the slopes "
+            "get no gradient"
+        )
+    other = ("segment_ids" if segment_ids is not None
+             else "window_size" if window is not None
+             else "softcap" if softcap > 0
+             else "block_mask" if block_mask is not None
+             else "fp8 inputs" if q.dtype == torch.float8_e4m3fn else None)
+    if other:
+        raise ValueError(
+            f"alibi_slopes and {other} are not supported together yet"
+        )
+    if q.shape[3] == 256 or q.shape[3] != v.shape[3]:
+        raise ValueError(
+            f"head_dim {q.shape[3]} (q, k) with {v.shape[3]} (v) with "
+            "alibi_slopes is not supported yet: the ALiBi tile kernels exist "
+            "for head_dim 64 and 128 only"
+        )
+    return t.reshape(-1, N).contiguous()
+
+
 _FP8 = torch.float8_e4m3fn
 
 
@@ -544,11 +637,13 @@ def _check_fp8(q, k, v, descale, segment_ids, window, softcap, block_mask):
     return tuple(float(x) for x in descale)
 
 
-def _op_args(ids, window, softcap, blocks=None, descale=None):
+def _op_args(ids, window, softcap, blocks=None, descale=None, alibi=None):
     """The trailing arguments of the two ops: the ids always, the window, the
-    cap, the block mask and the fp8 descales only when given, so that a call
-    without them applies the op with the argument list it had before they
-    existed."""
+    cap, the block mask, the fp8 descales and the ALiBi slopes only when given,
+    so that a call without them applies the op with the argument list it had
+    before they existed."""
+    if alibi is not None:  # never with any of the others
+        return (None, None, 0.0, None, 64, None, alibi)
     if descale is not None:  # never with ids, a window, a cap or a mask
         return (None, None, 0.0, None, 64, descale)
     if blocks is not None:
@@ -576,6 +671,7 @@ def burst_attn_func(
     block_mask: torch.Tensor = None,
     block_size: int = 64,
     descale=None,
+    alibi_slopes: torch.Tensor = None,
 ):
     _check_heads(q, k, v)
     window = _check_window(window_size, causal, segment_ids)
@@ -586,11 +682,13 @@ def burst_attn_func(
                          block_mask)
     blocks = _check_block_mask(block_mask, block_size, q, k, causal,
                                segment_ids, window, softcap)
+    alibi = _check_alibi(alibi_slopes, q, k, v, segment_ids, window, softcap,
+                         block_mask)
     return OpBurstAttn.apply(
         q, k, v, softmax_scale, flash, causal, optimize_bwd_comm,
         deterministic, process_group, double_group,
         *_op_args(_check_segment_ids(segment_ids, q), window, softcap, blocks,
-                  descale),
+                  descale, alibi),
     )
 
 
@@ -612,6 +710,7 @@ def burst_attn_func_striped(
     block_mask: torch.Tensor = None,
     block_size: int = 64,
     descale=None,
+    alibi_slopes: torch.Tensor = None,
 ):
     _check_heads(q, k, v)
     if block_mask is not None:
@@ -625,11 +724,13 @@ def burst_attn_func_striped(
     softcap = _check_softcap(softcap, segment_ids, window)
     _check_masks_for_mla_widths(q, v, segment_ids, window, softcap, None)
     descale = _check_fp8(q, k, v, descale, segment_ids, window, softcap, None)
+    alibi = _check_alibi(alibi_slopes, q, k, v, segment_ids, window, softcap,
+                         None)
     return OpBurstAttnStrip.apply(
         q, k, v, softmax_scale, flash, causal, optimize_bwd_comm,
         deterministic, process_group, double_group,
         *_op_args(_check_segment_ids(segment_ids, q), window, softcap,
-                  descale=descale),
+                  descale=descale, alibi=alibi),
     )
 
 
@@ -637,15 +738,19 @@ def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
                   causal=False, optimize_bwd_comm=False, deterministic=False,
                   process_group=None, double_group=[None, None],
                   segment_ids=None, window=None, softcap=0.0, block_mask=None,
-                  block_size=64, descale=None):
+                  block_size=64, descale=None, alibi=None):
     """Forward of both layouts: q stays, {k, v} travel the ring (with the
     kv ids, when there are segment ids).  With a window every round is the
     sub-tiles of ``window_tiles``, merged into a state that starts empty; with
     a block mask those of ``block_tiles``, each on its view of the rank's slab.
     With a cap every round's tile call carries it.  With fp8 inputs (``descale``
     given) k and v travel as uint8 views of their bytes, every round's tile
-    call carries the descales, o is bf16 and nothing is saved."""
+    call carries the descales, o is bf16 and nothing is saved.  With ALiBi
+    slopes every round is the tile calls of ``alibi_tiles``, each with the
+    position offset and stride of its piece pair, into a state that starts
+    empty."""
     _check_flash_arg(flash)
+    ctx.alibi = alibi
     ctx.segment_ids = ids = segment_ids
     ctx.blocks = None if block_mask is None else (block_mask, block_size)
     ctx.window = window
@@ -684,6 +789,9 @@ def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
     if window is not None:
         state = P.fwd_empty_state(q)
         wlayout = _window_layout(layout, causal)
+    if alibi is not None:
+        state = P.fwd_empty_state(q)
+        wlayout = _window_layout(layout, causal)
     if block_mask is not None:
         if block_mask.shape[3] != W * block_mask.shape[2]:
             raise ValueError(
@@ -699,7 +807,7 @@ def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
     for r in range(1, W + 1):
         src = get_partition_id(double_group, r, process_group)
         record.append(src)
-        if window is None and block_mask is None:
+        if window is None and block_mask is None and alibi is None:
             qw, kw, tile_causal = tile_window(layout, rank, src, causal, q.shape[1])
         payload = [k, v] if ids is None else [k, v, kv_ids]
         if r != W:
@@ -712,6 +820,12 @@ def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
                     state, q[:, qw], k[:, kw], v[:, kw], scale, tile_causal,
                     row_offset=qw.start,
                     **({} if band is None else {"band": band}))
+        elif alibi is not None:
+            for qw, kw, off, stride, tile_causal in alibi_tiles(
+                    wlayout, rank, src, W, q.shape[1], causal):
+                state = P.fwd_accum(
+                    state, q[:, qw], k[:, kw], v[:, kw], scale, tile_causal,
+                    row_offset=qw.start, alibi=(alibi, off, stride))
         elif block_mask is not None:
             for qw, kw, kv0, tile_causal in block_tiles(
                     rank, src, W, q.shape[1], causal):
@@ -793,6 +907,7 @@ def _ring_backward(layout, ctx, grad_output):
     blocks = ctx.blocks
     q_slab = None if blocks is None else replicate(blocks[0])
     window = ctx.window
+    alibi = ctx.alibi
     cap = {"softcap": ctx.softcap} if ctx.softcap > 0 else {}
     P = get_tile_provider()
     scale, causal = ctx.softmax_scale, ctx.causal
@@ -828,7 +943,7 @@ def _ring_backward(layout, ctx, grad_output):
         read_bufs.append(torch.empty_like(q_slab))
     for r in range(1, W + 1):
         src = get_partition_id(double_group, r, group)
-        if window is None and blocks is None:
+        if window is None and blocks is None and alibi is None:
             qw, kw, tile_causal = tile_window(layout, src, rank, causal, q.shape[1])
         payload = [dlt, grad_output, q, lse]
         if ids is not None:
@@ -857,6 +972,19 @@ def _ring_backward(layout, ctx, grad_output):
                 )
             # the dq fold below covers the union of the round's q rows (an
             # empty slice when the round computed nothing)
+            qw = slice(min((t[0].start for t in tiles), default=0),
+                       max((t[0].stop for t in tiles), default=0))
+        elif alibi is not None:
+            tiles = alibi_tiles(_window_layout(layout, causal), src, rank, W,
+                                q.shape[1], causal)
+            for qr, kr, off, stride, tile_causal in tiles:
+                P.bwd_accum(
+                    grad_output[:, qr], q[:, qr], k[:, kr], v[:, kr],
+                    delta[:, :, qr], lse[:, :, qr], scale, tile_causal,
+                    ctx.deterministic, tgt[:, qr], dk[:, kr], dv[:, kr],
+                    alibi=(alibi, off, stride),
+                )
+            # the dq fold covers the union of the round's q rows
             qw = slice(min((t[0].start for t in tiles), default=0),
                        max((t[0].stop for t in tiles), default=0))
         elif blocks is not None:
@@ -901,7 +1029,8 @@ def _ring_backward(layout, ctx, grad_output):
         dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype),
         None, None, None, None, None, None, None, None,
         # one None per trailing argument of _op_args beyond the ids
-        *((None,) * 4 if blocks is not None else (None, None) if cap
+        *((None,) * 6 if alibi is not None
+          else (None,) * 4 if blocks is not None else (None, None) if cap
           else () if window is None else (None,)),
     )
 

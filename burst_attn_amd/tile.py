@@ -106,6 +106,21 @@ unchanged.  There is no backward; ``seg``, ``band``, ``softcap`` and
 ``blocks`` with fp8 are refused.  A caller without fp8 inputs passes no
 ``descale`` keyword at all.
 
+ALiBi: ``fwd``, ``fwd_accum``, ``bwd`` and ``bwd_accum`` take an optional
+keyword ``alibi=(slopes, offset, stride)``: an fp32 tensor ``[1 or B, N]``,
+contiguous, on q's device, with one slope per *query* head, and two Python
+ints, ``stride >= 1``.  Pair (q row i, kv row j) *of the tensors passed* then
+gets the bias ``-slopes[b, h] * |stride * (i - j) + offset|`` added to its
+score ``q.k * scale`` before the softmax; ``causal`` applies as without it and
+``lse`` is the log-sum-exp of the biased scores.  The two ints place the
+tensors in a longer sequence: a contiguous piece pair has ``stride = 1`` and
+``offset = Pq - Pk``, the global positions of their first rows; rows dealt
+round-robin to W ranks have ``stride = W``.  The state of ``fwd_accum`` keeps
+its contract, so rounds with different offsets merge.  The slopes get no
+gradient.  head_dim 64 and 128; ``alibi`` with ``seg``, ``band``,
+``softcap``, ``blocks``, unequal widths or fp8 inputs is refused.  A caller
+without ALiBi passes no ``alibi`` keyword at all.
+
 The default provider is the gfx950 HIP extension and FAILS LOUDLY if the
 extension is missing on a GPU machine — there is no CPU/eager fallback in
 the product path.  Tests may inject an oracle-backed provider via
@@ -188,6 +203,26 @@ class HipTileProvider:
         return {"block_mask": mask2d, "block_size": int(bs)}
 
     @staticmethod
+    def _alibi_kw(alibi, q, v, seg, band, softcap, blocks):
+        """The extension's keywords of an ``alibi=(slopes, offset, stride)``;
+        none without."""
+        if alibi is None:
+            return {}
+        other = ("seg" if seg is not None else "band" if band is not None
+                 else "softcap" if softcap else "blocks" if blocks is not None
+                 else "fp8 inputs" if q.dtype == torch.float8_e4m3fn else None)
+        if other:
+            raise RuntimeError(
+                f"alibi and {other} are not supported together yet")
+        if q.shape[3] != v.shape[3]:
+            raise RuntimeError(
+                f"head_dim pair ({q.shape[3]}, {v.shape[3]}) does not "
+                "support alibi (plain calls only)")
+        slopes, offset, stride = alibi
+        return {"alibi_slopes": slopes, "alibi_offset": int(offset),
+                "alibi_stride": int(stride)}
+
+    @staticmethod
     def _check_plain_widths(q, v, seg, band, softcap, blocks):
         """Unequal q/k and v widths have the plain kernel form only."""
         if q.shape[3] == v.shape[3]:
@@ -218,7 +253,11 @@ class HipTileProvider:
         return {"descale": (float(sq), float(sk), float(sv))}
 
     def fwd(self, q, k, v, scale, causal, seg=None, band=None, softcap=None,
-            blocks=None, descale=None):
+            blocks=None, descale=None, alibi=None):
+        al_kw = self._alibi_kw(alibi, q, v, seg, band, softcap, blocks)
+        if al_kw:
+            return self._ext.attn_fwd(q, k, v, float(scale), bool(causal),
+                                      **al_kw)
         self._check_plain_widths(q, v, seg, band, softcap, blocks)
         fp8_kw = self._fp8_kw(q, descale, seg, band, softcap, blocks)
         if fp8_kw:
@@ -234,7 +273,12 @@ class HipTileProvider:
         return self._ext.attn_bwd_preprocess(o, do, out)
 
     def bwd(self, do, q, k, v, delta, lse, scale, causal, deterministic,
-            seg=None, band=None, softcap=None, blocks=None):
+            seg=None, band=None, softcap=None, blocks=None, alibi=None):
+        al_kw = self._alibi_kw(alibi, q, v, seg, band, softcap, blocks)
+        if al_kw:
+            return self._ext.attn_bwd(
+                do, q, k, v, delta, lse, float(scale), bool(causal),
+                bool(deterministic), **al_kw)
         self._check_plain_widths(q, v, seg, band, softcap, blocks)
         q_seg, kv_seg = seg if seg is not None else (None, None)
         return self._ext.attn_bwd(
@@ -245,7 +289,14 @@ class HipTileProvider:
         )
 
     def bwd_accum(self, do, q, k, v, delta, lse, scale, causal, deterministic,
-                  dq, dk, dv, seg=None, band=None, softcap=None, blocks=None):
+                  dq, dk, dv, seg=None, band=None, softcap=None, blocks=None,
+                  alibi=None):
+        al_kw = self._alibi_kw(alibi, q, v, seg, band, softcap, blocks)
+        if al_kw:
+            self._ext.attn_bwd_accum(
+                do, q, k, v, delta, lse, float(scale), bool(causal),
+                bool(deterministic), dq, dk, dv, **al_kw)
+            return
         self._check_plain_widths(q, v, seg, band, softcap, blocks)
         q_seg, kv_seg = seg if seg is not None else (None, None)
         self._ext.attn_bwd_accum(
@@ -263,7 +314,9 @@ class HipTileProvider:
     # running max, l fp32 [B,N,S] running sum) over the rank's FULL chunk;
     # row_offset targets the zigzag-half / striped-shift row windows.
     def fwd_accum(self, state, q, k, v, scale, causal, row_offset=0, seg=None,
-                  band=None, softcap=None, blocks=None, descale=None):
+                  band=None, softcap=None, blocks=None, descale=None,
+                  alibi=None):
+        al_kw = self._alibi_kw(alibi, q, v, seg, band, softcap, blocks)
         self._check_plain_widths(q, v, seg, band, softcap, blocks)
         fp8_kw = self._fp8_kw(q, descale, seg, band, softcap, blocks)
         cap_kw = self._cap_kw(softcap, seg, band)
@@ -271,7 +324,9 @@ class HipTileProvider:
         # the .s-built module carries the D=128 production variants only,
         # and no segment, band, soft-capped or block form: with any of them
         # the in-binary kernel runs
-        if fp8_kw:  # a kernel set of its own, never the module kernel
+        if al_kw:  # the in-binary ALiBi kernel, never the module kernel
+            accum = functools.partial(self._ext.attn_fwd_accum, **al_kw)
+        elif fp8_kw:  # a kernel set of its own, never the module kernel
             accum = functools.partial(self._ext.attn_fwd_accum, **fp8_kw)
         elif (self._asm_fwd and q.shape[3] == 128 and v.shape[3] == 128
                 and seg is None

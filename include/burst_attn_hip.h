@@ -188,6 +188,33 @@
  *     BAHIP_ERR_UNSUPPORTED naming what was asked.  Nothing is launched by a
  *     refused call.  There is no backward and no mask form.  Every other
  *     entry point keeps refusing BAHIP_F8E4M3 as an unknown dtype code.
+ *   - ALiBi (the flash-attn `alibi_slopes` argument): the *_alibi entry
+ *     points take, before stream, slopes (fp32, one per QUERY head, head
+ *     stride 1), slopes_batch_stride (elements between batch rows, 0 = one row
+ *     shared by the batch), pos_offset and pos_stride.  Pair (q row i, kv row
+ *     j) of the tensors passed gets the score
+ *     q_i.k_j * softmax_scale - slopes[b][h] * |pos_stride * (i - j) +
+ *     pos_offset|; the causal / rectangular rule of the call then applies as
+ *     without it.  The two integers place the tensors in a longer sequence: a
+ *     contiguous pair of pieces has pos_stride = 1 and pos_offset = (global
+ *     position of q row 0) - (that of kv row 0); rows dealt round-robin to W
+ *     ranks have pos_stride = W.  lse is the natural-log sum-exp of the biased
+ *     scores, o, dq, dk and dv are those of softmax over the biased scores
+ *     times V, the slopes get no gradient; the state contract, finalize, state
+ *     init and the preprocess are unchanged, so rounds with different offsets
+ *     merge through (acc, m, l) as plain rounds do.  The bias is computed in
+ *     registers from the accumulator position, two FMAs per score; nothing is
+ *     read but one slope per workgroup (per group member in dK/dV).  Null
+ *     slopes is exactly the *_gqa entry point.  pos_stride < 1, or
+ *     |pos_offset| + pos_stride * max(Sq, Sk) above 2^30 (the distance is an
+ *     int32), returns BAHIP_ERR_ALIBI.  D = 64 / 128, fp16 and bf16, GQA,
+ *     strided slices; the backward is as bitwise deterministic as the plain
+ *     kernels.  D = 256, a BA_FWD_* selection other than the default variant,
+ *     BA_BWD_FUSED=1/2, BA_BWD_DK_FLIP=1, BA_DQ_PIPE=1 and a non-null
+ *     hip_function return BAHIP_ERR_UNSUPPORTED naming what was asked.
+ *     Nothing is launched by a refused call.  The forward transposes V in the
+ *     kernel whatever BA_FWD_VT says.  Slopes together with segment ids, a
+ *     band, a cap, a block mask, unequal widths or fp8 have no entry point.
  *   - stream is a hipStream_t.
  * Returns 0 on success; nonzero = error.  Every nonzero return sets the
  * calling thread's bahip_last_error() message and every success clears it.
@@ -228,6 +255,9 @@ extern "C" {
 
 #define BAHIP_ERR_DESCALE 1010        /* an fp8 descale not positive or not
                                          finite */
+
+#define BAHIP_ERR_ALIBI 1011          /* pos_stride < 1, or a position
+                                         distance beyond 2^30 */
 
 const char* bahip_last_error(void);
 
@@ -504,6 +534,43 @@ int bahip_attn_bwd_softcap(
     const int64_t dv_strides[3],
     float softmax_scale, int causal, int deterministic, int dtype,
     float softcap, void* stream);
+
+/* ---- ALiBi (see "ALiBi" above) --------------------------------------------
+ * bahip_attn_fwd_gqa, bahip_attn_fwd_accum_gqa and bahip_attn_bwd_gqa with
+ * per-head linear position biases. */
+int bahip_attn_fwd_alibi(
+    const void* q, const void* k, const void* v,
+    float* o, float* lse,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3],
+    const int64_t k_strides[3],
+    const int64_t v_strides[3],
+    float softmax_scale, int causal, int dtype,
+    const float* slopes, int64_t slopes_batch_stride, int64_t pos_offset,
+    int64_t pos_stride, void* stream);
+int bahip_attn_fwd_accum_alibi(
+    void* hip_function,
+    const void* q, const void* k, const void* v,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    float* acc, float* m, float* l, const int64_t acc_strides[3],
+    const int64_t ml_strides[2], int carry_in,
+    const float* slopes, int64_t slopes_batch_stride, int64_t pos_offset,
+    int64_t pos_stride, void* stream);
+int bahip_attn_bwd_alibi(
+    const void* dout, const void* q, const void* k, const void* v,
+    const float* delta, const float* lse,
+    float* dq, float* dk, float* dv,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t do_strides[3], const int64_t q_strides[3],
+    const int64_t k_strides[3], const int64_t v_strides[3],
+    const int64_t delta_strides[2], const int64_t lse_strides[2],
+    const int64_t dq_strides[3], const int64_t dk_strides[3],
+    const int64_t dv_strides[3],
+    float softmax_scale, int causal, int deterministic, int dtype,
+    const float* slopes, int64_t slopes_batch_stride, int64_t pos_offset,
+    int64_t pos_stride, void* stream);
 
 /* ---- block masks (see "block masks" above) --------------------------------
  * bahip_attn_fwd_gqa, bahip_attn_fwd_accum_gqa and bahip_attn_bwd_gqa with a
