@@ -8,6 +8,8 @@ Public API (drop-in for the reference ``burst_attn`` package):
     burst_attn_func, burst_attn_func_striped
 Beyond the reference: packed sequences (``segment_ids=``), with the helpers
     segment_ids_from_cu_seqlens, local_segment_ids
+and block-scaled FP8 inputs (``descale=`` tensors), with the HIP quantiser
+    quantize_fp8
 """
 
 from .interface import (  # noqa: F401
@@ -15,6 +17,7 @@ from .interface import (  # noqa: F401
     burst_attn_func_striped,
     OpBurstAttn,
     OpBurstAttnStrip,
+    quantize_fp8,
 )
 from .segments import (  # noqa: F401
     local_segment_ids,

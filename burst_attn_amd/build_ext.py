@@ -20,7 +20,7 @@ DEVICE_SOURCES = ["attn_fwd.hip", "attn_bwd.hip", "probes.hip",
                   "attn_fwd_softcap.hip", "attn_bwd_softcap.hip",
                   "attn_fwd_blk.hip", "attn_bwd_blk.hip",
                   "attn_hd192_fwd.hip", "attn_hd192_bwd.hip",
-                  "attn_fp8_fwd.hip",
+                  "attn_fp8_fwd.hip", "attn_fp8_quant.hip",
                   "attn_fwd_alibi.hip", "attn_bwd_alibi.hip"]
 # Per-source compiler flags.  The head_dim 256 kernels are built without
 # packed fp32 VALU ops (v_pk_mul_f32 and kin): the accumulator rescale is

@@ -72,11 +72,48 @@
 //   rows.
 //   Unswizzled, both reads would be 8-way (K) and 4-way (V^T) conflicts.
 //
+// Block-scaled form (ba_fp8_scale_args in the kernel's trailing pack; an empty
+// pack is the per-tensor kernel above, text for text).  Real values are
+// q8 * dq[row], k8 * dk[kv tile], v8 * dv[channel]:
+//   dq: a lane of S^T owns one q row, so dq[row] folds into that lane's exp2
+//   multiplier once per call: c2 = softmax_scale * log2(e) * dq[row].
+//   dk: one value per 64-row kv tile, multiplied into c2 for that tile.  The
+//   scale is positive, so the row max of the raw scores of ONE tile still
+//   commutes with it; across tiles m lives in real exp2 units as before.  The
+//   value of tile t + 1 is fetched with tile t + 1's staging loads, one tile
+//   ahead of its use, and handed on in a register: no tile waits on it.
+//   dv: one value per v channel of this call.  The accumulator row of channel
+//   d is kept in units of dv[d] / c for the whole call: the carry-in value is
+//   multiplied by c / dv[d], the result by dv[d] / c.  The 128 quotients
+//   c / dv[d] are formed once per workgroup, in LDS (512 bytes behind the tile
+//   buffers), not 64 divisions per lane; after the loop the same 512 bytes
+//   hold dv[d] / c for the store.  Nothing of dv is per tile.
+// (acc, m, l) stay fp32 in real units, so rounds with different scales merge.
+// The scales must be positive and finite; the quantiser (attn_fp8_quant.hip)
+// writes no other.
+//
 // No segment-id, band, soft-capped, block, module or experiment-variant form
 // exists here: the entry points refuse those.
 #pragma once
 #include "attn_common.h"
 #include "attn_host.h"
+
+// The scale tensors of a block-scaled call, fp32, innermost stride 1:
+// dq [B][N][Sq], dk [B][Nk][>= k_tile0 + ceil(Sk/64)], dv [B][Nk][128].
+// k_tile0 is the dk index of the call's first kv tile.
+struct ba_fp8_scale_args {
+  const float* dq;
+  const float* dk;
+  const float* dv;
+  int64_t dq_sb, dq_sh;  // batch / head strides in elements
+  int64_t dk_sb, dk_sh;
+  int64_t dv_sb, dv_sh;
+  int k_tile0;
+};
+__device__ __forceinline__ ba_fp8_scale_args ba_fp8_scale_of(
+    const ba_fp8_scale_args& s) {
+  return s;
+}
 
 constexpr int BA_FP8_D = 128;      // head_dim, q/k/v/o alike
 constexpr int BA_FP8_BLOCK = 128;  // q rows a workgroup owns (4 waves x 32)

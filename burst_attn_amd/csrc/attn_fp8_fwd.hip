@@ -16,6 +16,9 @@
 //     fragments (2 x 8 dwords).
 //   * OUT_STATE as in attn_fwd.hip: 0 = normalised o + lse, 1 = the carry-in
 //     / carry-out state (acc, m, l), bit-compatible with the D = 128 kernels'.
+//   * SC: empty = per-tensor descales folded into fp8_extra by the host.  One
+//     ba_fp8_scale_args = the block-scaled form (attn_fp8.h): dq per q row,
+//     dk per kv tile, dv per v channel, read from device tensors.
 
 #include "attn_fp8.h"
 #include "fwd_variants.h"
@@ -78,8 +81,11 @@ __global__ __launch_bounds__(BA_FP8_NT) void attn_fp8_vt_kernel(
 // 164 + 96 registers over both files, 4 past what two workgroups per CU
 // allow; asked for two it needs 167 in all, no AGPRs and no scratch, and
 // three workgroups fit a CU (32 KiB of LDS each).
-template <int OUT_STATE>
-__global__ __launch_bounds__(BA_FP8_NT, 2) void attn_fp8_fwd_kernel(
+// The scaled form asks for three: its LDS multipliers let the compiler batch
+// the epilogue's reads into 185 registers otherwise, one workgroup per CU less.
+template <int OUT_STATE, typename... SC>
+__global__ __launch_bounds__(BA_FP8_NT, sizeof...(SC) ? 3 : 2) void
+attn_fp8_fwd_kernel(
     const char* __restrict__ q, const char* __restrict__ k,
     float* __restrict__ o, float* __restrict__ lse,
     int Sq, int Sk, int N, int G,
@@ -89,15 +95,20 @@ __global__ __launch_bounds__(BA_FP8_NT, 2) void attn_fp8_fwd_kernel(
     float* __restrict__ st_acc, float* __restrict__ st_m,
     float* __restrict__ st_l,
     int64_t a_sb, int64_t a_ss, int64_t a_sh,
-    int64_t ml_sb, int64_t ml_sh, int carry_in, fp8_extra x) {
+    int64_t ml_sb, int64_t ml_sh, int carry_in, fp8_extra x, SC... sc) {
+  constexpr bool HAS_SC = ba_pack_is<ba_fp8_scale_args, SC...>;
+  static_assert(HAS_SC || sizeof...(SC) == 0,
+                "the pack: one ba_fp8_scale_args");
   constexpr int D = BA_FP8_D;
   constexpr int NT = BA_FP8_NT;
   constexpr int KVBLK = BA_FP8_KVBLK;
   constexpr int TILEB = KVBLK * D;  // bytes of a K tile and of a V^T block
   constexpr int PT = TILEB / 16 / NT;  // 2 chunks of each per thread
 
-  // [2 buffers][K row-major | V^T], both swizzled (attn_fp8.h)
-  __shared__ __attribute__((aligned(16))) char lds[2 * 2 * TILEB];
+  // [2 buffers][K row-major | V^T], both swizzled (attn_fp8.h); the scaled
+  // form keeps the 128 carry-in multipliers c / dv[d] behind them
+  __shared__ __attribute__((aligned(16))) char
+      lds[2 * 2 * TILEB + (HAS_SC ? D * (int)sizeof(float) : 0)];
   auto ldsK = [&](int buf) -> char* { return lds + buf * 2 * TILEB; };
   auto ldsVT = [&](int buf) -> char* { return lds + buf * 2 * TILEB + TILEB; };
 
@@ -132,7 +143,24 @@ __global__ __launch_bounds__(BA_FP8_NT, 2) void attn_fp8_fwd_kernel(
     qf[i] = ba_fp8_join(w0, w1);
   }
 
-  const float c2 = x.c2;
+  // scaled form: x.c2 is softmax_scale * log2(e) alone; the row's dq joins
+  // it here, the tile's dk in the loop
+  float c2q = x.c2;
+  const float* dkp = nullptr;
+  const float* dvp = nullptr;
+  float dk_cur = 1.f, dk_next = 1.f;
+  if constexpr (HAS_SC) {
+    const ba_fp8_scale_args sa = ba_fp8_scale_of(sc...);
+    if (q_row < Sq) c2q *= sa.dq[b * sa.dq_sb + n * sa.dq_sh + q_row];
+    dkp = sa.dk + b * sa.dk_sb + nkv * sa.dk_sh + sa.k_tile0;
+    dvp = sa.dv + b * sa.dv_sb + nkv * sa.dv_sh;
+    dk_cur = dkp[0];
+    if (OUT_STATE && carry_in) {  // uniform: the whole grid takes one side
+      if (tid < D)
+        ((float*)(lds + 2 * 2 * TILEB))[tid] = BA_FP8_PSCALE / dvp[tid];
+      __syncthreads();
+    }
+  }
   constexpr float LOG2C = 4.f;  // log2(BA_FP8_PSCALE)
   static_assert(BA_FP8_PSCALE == 16.f, "LOG2C follows BA_FP8_PSCALE");
   float m2 = BA_NEG_BIG;
@@ -148,7 +176,12 @@ __global__ __launch_bounds__(BA_FP8_NT, 2) void attn_fp8_fwd_kernel(
     for (int dt = 0; dt < D / 32; ++dt)
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        ot[dt][r] = arow[dt * 32 + ba_crow(r, hi)] * x.in_mul;
+        if constexpr (HAS_SC)
+          ot[dt][r] = arow[dt * 32 + ba_crow(r, hi)] *
+                      ((const float*)(lds + 2 * 2 * TILEB))[dt * 32 +
+                                                           ba_crow(r, hi)];
+        else
+          ot[dt][r] = arow[dt * 32 + ba_crow(r, hi)] * x.in_mul;
   }
 
   // causal: no key past the block's last row is visible to any of its rows
@@ -192,7 +225,12 @@ __global__ __launch_bounds__(BA_FP8_NT, 2) void attn_fp8_fwd_kernel(
     const int kv0 = t * KVBLK;
     const bool has_next = (t + 1) < nt;
     u32x4_t kreg[PT], vreg[PT];
-    if (has_next) issue_loads(t + 1, kreg, vreg);
+    if (has_next) {
+      issue_loads(t + 1, kreg, vreg);
+      // the next tile's dk rides with its staging loads, a tile ahead of use
+      if constexpr (HAS_SC) dk_next = dkp[t + 1];
+    }
+    const float c2 = HAS_SC ? c2q * dk_cur : c2q;
 
     // causal: a tile wholly above the diagonal of this wave's 32 rows
     if (!causal || kv0 <= qb + 31) {
@@ -222,7 +260,7 @@ __global__ __launch_bounds__(BA_FP8_NT, 2) void attn_fp8_fwd_kernel(
               s[kvs][r] = BA_NEG_BIG;
           }
       }
-      // row max on raw scores (max commutes with c2 > 0)
+      // row max on raw scores (max commutes with c2 > 0, one c2 per tile)
       float tm = fmaxf(ba_max16(s[0]), ba_max16(s[1]));
       {
         float lo, hi2;
@@ -276,6 +314,18 @@ __global__ __launch_bounds__(BA_FP8_NT, 2) void attn_fp8_fwd_kernel(
     if (has_next) write_lds(cur ^ 1, kreg, vreg);
     __syncthreads();
     cur ^= 1;
+    if constexpr (HAS_SC) dk_cur = dk_next;
+  }
+
+  // scaled form: the 128 store multipliers dv[d] / c take the LDS slot the
+  // carry-in multipliers had (read before the loop's first barrier; the
+  // loop's last barrier is behind every wave here)
+  const float* outm = (const float*)(lds + 2 * 2 * TILEB);
+  if constexpr (HAS_SC) {
+    if (tid < D)
+      ((float*)(lds + 2 * 2 * TILEB))[tid] =
+          dvp[tid] * (1.f / BA_FP8_PSCALE);
+    __syncthreads();
   }
 
   if (q_row < Sq) {
@@ -285,42 +335,53 @@ __global__ __launch_bounds__(BA_FP8_NT, 2) void attn_fp8_fwd_kernel(
       for (int dt = 0; dt < D / 32; ++dt)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          arow[dt * 32 + ba_crow(r, hi)] = ot[dt][r] * x.out_mul;
+          if constexpr (HAS_SC)
+            arow[dt * 32 + ba_crow(r, hi)] =
+                ot[dt][r] * outm[dt * 32 + ba_crow(r, hi)];
+          else
+            arow[dt * 32 + ba_crow(r, hi)] = ot[dt][r] * x.out_mul;
       if (hi == 0) {
         st_m[b * ml_sb + n * ml_sh + q_row] = m2;
         st_l[b * ml_sb + n * ml_sh + q_row] = lsum;
       }
     } else {
-      const float inv_l = x.out_mul / lsum;
+      // scaled form: dv[d] / c is per channel, 1 / l per row
+      const float inv_l = (HAS_SC ? 1.f : x.out_mul) / lsum;
       float* orow = o + (((int64_t)b * Sq + q_row) * N + n) * D;
 #pragma unroll
       for (int dt = 0; dt < D / 32; ++dt)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          orow[dt * 32 + ba_crow(r, hi)] = ot[dt][r] * inv_l;
+          if constexpr (HAS_SC)
+            orow[dt * 32 + ba_crow(r, hi)] =
+                ot[dt][r] * outm[dt * 32 + ba_crow(r, hi)] * inv_l;
+          else
+            orow[dt * 32 + ba_crow(r, hi)] = ot[dt][r] * inv_l;
       if (hi == 0)
         lse[((int64_t)b * N + n) * Sq + q_row] = BA_LN2 * (m2 + log2f(lsum));
     }
   }
 }
 
-template <int OUT_STATE>
+template <int OUT_STATE, typename... SC>
 void launch_fp8_fwd(const fwd_args& a, const fp8_extra& x, int64_t B,
-                    hipStream_t stream) {
+                    hipStream_t stream, SC... sc) {
   const dim3 grid((unsigned)((a.Sq + BA_FP8_BLOCK - 1) / BA_FP8_BLOCK),
                   (unsigned)a.N, (unsigned)B);
-  attn_fp8_fwd_kernel<OUT_STATE><<<grid, dim3(BA_FP8_NT), 0, stream>>>(
+  attn_fp8_fwd_kernel<OUT_STATE, SC...><<<grid, dim3(BA_FP8_NT), 0, stream>>>(
       (const char*)a.q, (const char*)a.k, a.o, a.lse, a.Sq, a.Sk, a.N, a.G,
       a.q_sb, a.q_ss, a.q_sh, a.k_sb, a.k_ss, a.k_sh, a.causal, a.st_acc,
-      a.st_m, a.st_l, a.a_sb, a.a_ss, a.a_sh, a.ml_sb, a.ml_sh, a.carry_in, x);
+      a.st_m, a.st_l, a.a_sb, a.a_ss, a.a_sh, a.ml_sb, a.ml_sh, a.carry_in, x,
+      sc...);
 }
 
 bool fp8_descale_ok(float d) { return __builtin_isfinite(d) && d > 0.f; }
 
 // The FP8 forward: the checks of the plain call and its own, the V^T image
 // pre-pass, then the one kernel.  Every refusal comes before any launch.
-int fp8_fwd_entry(int out_state, const void* q, const void* k, const void* v,
-                  float* o, float* lse, int64_t B, int64_t Sq, int64_t Sk,
+// `sa` non-null is the block-scaled call: the three floats are then ones.
+int fp8_fwd_entry(const ba_fp8_scale_args* sa, int out_state, const void* q,
+                  const void* k, const void* v, float* o, float* lse, int64_t B, int64_t Sq, int64_t Sk,
                   int64_t N, int64_t Nk, int64_t D, const int64_t* qs,
                   const int64_t* ks, const int64_t* vs, float scale,
                   int causal, int dtype, float* acc, float* m, float* l,
@@ -344,6 +405,12 @@ int fp8_fwd_entry(int out_state, const void* q, const void* k, const void* v,
                    "q heads N=%d must be a positive multiple of kv heads "
                    "Nk=%d",
                    (int)N, (int)Nk);
+  if (sa && (!sa->dq || !sa->dk || !sa->dv || sa->k_tile0 < 0))
+    return ba_fail(BAHIP_ERR_DESCALE,
+                   "fp8 scaled forward: descale tensors (%p, %p, %p) must "
+                   "all be given and k_tile0 = %d must not be negative",
+                   (const void*)sa->dq, (const void*)sa->dk,
+                   (const void*)sa->dv, sa->k_tile0);
   if (!fp8_descale_ok(dq) || !fp8_descale_ok(dk) || !fp8_descale_ok(dv))
     return ba_fail(BAHIP_ERR_DESCALE,
                    "fp8 descale (%g, %g, %g): every entry must be positive "
@@ -419,10 +486,16 @@ int fp8_fwd_entry(int out_state, const void* q, const void* k, const void* v,
                        dim3(BA_FP8_NT), 0, (hipStream_t)stream>>>(
       (const char*)v, (char*)ws, (int)Sk, (int)Nk, vs[0], vs[1], vs[2]);
   BA_CHECK_LAUNCH();
-  if (out_state)
+  if (sa) {
+    if (out_state)
+      launch_fp8_fwd<1>(a, x, B, (hipStream_t)stream, *sa);
+    else
+      launch_fp8_fwd<0>(a, x, B, (hipStream_t)stream, *sa);
+  } else if (out_state) {
     launch_fp8_fwd<1>(a, x, B, (hipStream_t)stream);
-  else
+  } else {
     launch_fp8_fwd<0>(a, x, B, (hipStream_t)stream);
+  }
   return ba_launch_status();
 }
 
@@ -440,7 +513,7 @@ extern "C" int bahip_attn_fwd_f8(
     const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
     float descale_q, float descale_k, float descale_v, void* workspace,
     int64_t workspace_bytes, void* stream) {
-  return fp8_fwd_entry(0, q, k, v, o, lse, B, Sq, Sk, N, Nk, D, q_strides,
+  return fp8_fwd_entry(nullptr, 0, q, k, v, o, lse, B, Sq, Sk, N, Nk, D, q_strides,
                        k_strides, v_strides, softmax_scale, causal, dtype,
                        nullptr, nullptr, nullptr, nullptr, nullptr, 0,
                        descale_q, descale_k, descale_v, workspace,
@@ -459,9 +532,64 @@ extern "C" int bahip_attn_fwd_accum_f8(
   if (hip_function)
     return ba_fail(BAHIP_ERR_UNSUPPORTED,
                    "fp8 does not support a module-launched forward");
-  return fp8_fwd_entry(1, q, k, v, nullptr, nullptr, B, Sq, Sk, N, Nk, D,
+  return fp8_fwd_entry(nullptr, 1, q, k, v, nullptr, nullptr, B, Sq, Sk, N, Nk, D,
                        q_strides, k_strides, v_strides, softmax_scale, causal,
                        dtype, acc, m, l, acc_strides, ml_strides, carry_in,
                        descale_q, descale_k, descale_v, workspace,
                        workspace_bytes, stream);
+}
+
+// ---- block-scaled entry points ---------------------------------------------
+namespace {
+ba_fp8_scale_args fp8_scale_args(const float* dq, const float* dk,
+                                 const float* dv, const int64_t* dqs,
+                                 const int64_t* dks, const int64_t* dvs,
+                                 int64_t k_tile0) {
+  static const int64_t none[2] = {0, 0};
+  if (!dqs || !dks || !dvs) dq = nullptr, dqs = dks = dvs = none;
+  const bool tile_ok = k_tile0 >= 0 && k_tile0 <= INT32_MAX / 2;
+  return {dq, dk, dv, dqs[0], dqs[1], dks[0], dks[1], dvs[0], dvs[1],
+          tile_ok ? (int)k_tile0 : -1};
+}
+}  // namespace
+
+extern "C" int bahip_attn_fwd_f8_scaled(
+    const void* q, const void* k, const void* v, float* o, float* lse,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    const float* descale_q, const float* descale_k, const float* descale_v,
+    const int64_t dq_strides[2], const int64_t dk_strides[2],
+    const int64_t dv_strides[2], int64_t k_tile0, void* workspace,
+    int64_t workspace_bytes, void* stream) {
+  const ba_fp8_scale_args sa =
+      fp8_scale_args(descale_q, descale_k, descale_v, dq_strides, dk_strides,
+                     dv_strides, k_tile0);
+  return fp8_fwd_entry(&sa, 0, q, k, v, o, lse, B, Sq, Sk, N, Nk, D, q_strides,
+                       k_strides, v_strides, softmax_scale, causal, dtype,
+                       nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1.f,
+                       1.f, 1.f, workspace, workspace_bytes, stream);
+}
+
+extern "C" int bahip_attn_fwd_accum_f8_scaled(
+    void* hip_function, const void* q, const void* k, const void* v,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    float* acc, float* m, float* l, const int64_t acc_strides[3],
+    const int64_t ml_strides[2], int carry_in, const float* descale_q,
+    const float* descale_k, const float* descale_v,
+    const int64_t dq_strides[2], const int64_t dk_strides[2],
+    const int64_t dv_strides[2], int64_t k_tile0, void* workspace,
+    int64_t workspace_bytes, void* stream) {
+  if (hip_function)
+    return ba_fail(BAHIP_ERR_UNSUPPORTED,
+                   "fp8 does not support a module-launched forward");
+  const ba_fp8_scale_args sa =
+      fp8_scale_args(descale_q, descale_k, descale_v, dq_strides, dk_strides,
+                     dv_strides, k_tile0);
+  return fp8_fwd_entry(&sa, 1, q, k, v, nullptr, nullptr, B, Sq, Sk, N, Nk, D,
+                       q_strides, k_strides, v_strides, softmax_scale, causal,
+                       dtype, acc, m, l, acc_strides, ml_strides, carry_in,
+                       1.f, 1.f, 1.f, workspace, workspace_bytes, stream);
 }

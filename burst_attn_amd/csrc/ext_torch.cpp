@@ -73,7 +73,74 @@ void check_qkv3(const at::Tensor& q, const at::Tensor& k,
               "q/k/v dtype mismatch");
 }
 
-using Descale = c10::optional<std::tuple<double, double, double>>;
+// descale= of an fp8 call: three Python floats (per tensor, the *_f8 entry
+// points) or three fp32 tensors (dq [B,N,Sq], dk [B,Nk,tiles], dv [B,Nk,128];
+// the *_f8_scaled entry points), never a mix.
+struct Descale {
+  bool given = false, tensors = false;
+  double f[3] = {1.0, 1.0, 1.0};
+  at::Tensor t[3];
+  int64_t k_tile0 = 0;
+  bool has_value() const { return given; }
+};
+
+Descale descale_of(const py::object& o, int64_t k_tile0) {
+  Descale d;
+  d.k_tile0 = k_tile0;
+  if (o.is_none()) {
+    TORCH_CHECK(k_tile0 == 0, "k_tile0 is for descale tensors only");
+    return d;
+  }
+  TORCH_CHECK((py::isinstance<py::tuple>(o) || py::isinstance<py::list>(o)) &&
+                  py::len(o) == 3,
+              "descale must be three floats or three tensors");
+  const auto seq = o.cast<py::sequence>();
+  int nt = 0;
+  for (int i = 0; i < 3; ++i) nt += THPVariable_Check(seq[i].ptr()) ? 1 : 0;
+  TORCH_CHECK(nt == 0 || nt == 3,
+              "descale must be three floats or three tensors, not a mix");
+  d.given = true;
+  d.tensors = nt == 3;
+  for (int i = 0; i < 3; ++i)
+    if (d.tensors)
+      d.t[i] = seq[i].cast<at::Tensor>();
+    else
+      d.f[i] = seq[i].cast<double>();
+  TORCH_CHECK(d.tensors || k_tile0 == 0,
+              "k_tile0 is for descale tensors only");
+  return d;
+}
+
+// The scale tensors of a block-scaled call against its q, k, v: everything
+// the kernel indexes is checked here, before anything is sized or launched.
+void check_scales(const Descale& d, const at::Tensor& q, const at::Tensor& k) {
+  static const char* const name[3] = {"descale q", "descale k", "descale v"};
+  const int64_t B = q.size(0), tiles = (k.size(1) + 63) / 64;
+  const int64_t want[3][3] = {{B, q.size(2), q.size(1)},
+                              {B, k.size(2), d.k_tile0 + tiles},
+                              {B, k.size(2), k.size(3)}};
+  TORCH_CHECK(d.k_tile0 >= 0, "descale: k_tile0 must not be negative");
+  for (int i = 0; i < 3; ++i) {
+    const at::Tensor& t = d.t[i];
+    TORCH_CHECK(t.defined() && t.scalar_type() == at::kFloat, name[i],
+                " must be an fp32 tensor");
+    TORCH_CHECK(t.device() == q.device(), name[i], " must be on q's device");
+    TORCH_CHECK(!t.requires_grad(), name[i], " must not require grad");
+    TORCH_CHECK(t.dim() == 3 && t.size(0) == want[i][0] &&
+                    t.size(1) == want[i][1] &&
+                    (i == 1 ? t.size(2) >= want[i][2]
+                            : t.size(2) == want[i][2]),
+                name[i], " must be [", want[i][0], ", ", want[i][1], ", ",
+                i == 1 ? ">= " : "", want[i][2], "], got ", t.sizes());
+    TORCH_CHECK(t.stride(2) == 1, name[i], " innermost dim must be contiguous");
+  }
+}
+
+struct Strides2 {
+  int64_t s[2];
+  explicit Strides2(const at::Tensor& t) : s{t.stride(0), t.stride(1)} {}
+  operator const int64_t*() const { return s; }
+};
 
 void check_fp8_plain(const c10::optional<at::Tensor>& q_seg,
                      const c10::optional<at::Tensor>& kv_seg,
@@ -351,9 +418,11 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k,
                                  const c10::optional<at::Tensor>& block_mask,
                                  int64_t block_size,
                                  const c10::optional<at::Tensor>& blk_ws,
-                                 const Descale& descale,
+                                 const py::object& descale_arg,
                                  const c10::optional<at::Tensor>& alibi_slopes,
-                                 int64_t alibi_offset, int64_t alibi_stride) {
+                                 int64_t alibi_offset, int64_t alibi_stride,
+                                 int64_t k_tile0) {
+  const Descale descale = descale_of(descale_arg, k_tile0);
   check_qkv3(q, k, v);
   const auto B = q.size(0), Sq = q.size(1), N = q.size(2), D = q.size(3);
   const auto Sk = k.size(1);
@@ -376,10 +445,23 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k,
   if (is_fp8(q)) {
     check_fp8_plain(q_seg, kv_seg, band_lo, band_hi, softcap, block_mask);
     check_fp8_widths(q, v);
-    const auto [dq, dk, dv] = descale.value_or(std::make_tuple(1.0, 1.0, 1.0));
+    if (descale.tensors) check_scales(descale, q, k);
+    const double dq = descale.f[0], dk = descale.f[1], dv = descale.f[2];
     auto o = at::empty({B, Sq, N, D}, q.options().dtype(at::kFloat));
     auto lse = at::empty({B, N, Sq}, q.options().dtype(at::kFloat));
     auto ws = fp8_workspace(k);
+    if (descale.tensors) {
+      const at::Tensor* t = descale.t;
+      BA_CALL(bahip_attn_fwd_f8_scaled(
+          q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr<float>(),
+          lse.data_ptr<float>(), B, Sq, Sk, N, k.size(2), D, Strides3(q),
+          Strides3(k), Strides3(v), (float)softmax_scale, causal ? 1 : 0,
+          BAHIP_F8E4M3, t[0].data_ptr<float>(), t[1].data_ptr<float>(),
+          t[2].data_ptr<float>(), Strides2(t[0]), Strides2(t[1]),
+          Strides2(t[2]), descale.k_tile0, ws.data_ptr(), ws.numel(),
+          at::hip::getCurrentHIPStream().stream()));
+      return {o, lse};
+    }
     BA_CALL(bahip_attn_fwd_f8(
         q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr<float>(),
         lse.data_ptr<float>(), B, Sq, Sk, N, k.size(2), D, Strides3(q),
@@ -497,7 +579,7 @@ void fwd_accum_call(void* asm_fn, const at::Tensor& q, const at::Tensor& k,
                     const c10::optional<at::Tensor>& block_mask = c10::nullopt,
                     int64_t block_size = 64,
                     const c10::optional<at::Tensor>& blk_ws = c10::nullopt,
-                    const Descale& descale = c10::nullopt,
+                    const Descale& descale = Descale(),
                     const c10::optional<at::Tensor>& alibi_slopes =
                         c10::nullopt,
                     int64_t alibi_offset = 0, int64_t alibi_stride = 1) {
@@ -507,6 +589,7 @@ void fwd_accum_call(void* asm_fn, const at::Tensor& q, const at::Tensor& k,
   if (is_fp8(q)) {
     check_fp8_plain(q_seg, kv_seg, band_lo, band_hi, softcap, block_mask);
     check_fp8_widths(q, v);
+    if (descale.tensors) check_scales(descale, q, k);
   } else
     TORCH_CHECK(!descale.has_value(),
                 "descale is for fp8 (float8_e4m3fn) inputs only, got ",
@@ -537,8 +620,21 @@ void fwd_accum_call(void* asm_fn, const at::Tensor& q, const at::Tensor& k,
     return;
   }
   if (is_fp8(q)) {
-    const auto [dq, dk, dv] = descale.value_or(std::make_tuple(1.0, 1.0, 1.0));
+    const double dq = descale.f[0], dk = descale.f[1], dv = descale.f[2];
     auto ws = fp8_workspace(k);
+    if (descale.tensors) {
+      const at::Tensor* t = descale.t;
+      BA_CALL(bahip_attn_fwd_accum_f8_scaled(
+          asm_fn, q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Sq, Sk, N,
+          k.size(2), D, Strides3(q), Strides3(k), Strides3(v),
+          (float)softmax_scale, causal ? 1 : 0, BAHIP_F8E4M3,
+          acc.data_ptr<float>(), m.data_ptr<float>(), l.data_ptr<float>(),
+          Strides3(acc), mls, carry_in ? 1 : 0, t[0].data_ptr<float>(),
+          t[1].data_ptr<float>(), t[2].data_ptr<float>(), Strides2(t[0]),
+          Strides2(t[1]), Strides2(t[2]), descale.k_tile0, ws.data_ptr(),
+          ws.numel(), at::hip::getCurrentHIPStream().stream()));
+      return;
+    }
     BA_CALL(bahip_attn_fwd_accum_f8(
         asm_fn, q.data_ptr(), k.data_ptr(), v.data_ptr(), B, Sq, Sk, N,
         k.size(2), D, Strides3(q), Strides3(k), Strides3(v),
@@ -617,13 +713,40 @@ void attn_fwd_accum(const at::Tensor& q, const at::Tensor& k,
                     const c10::optional<at::Tensor>& block_mask,
                     int64_t block_size,
                     const c10::optional<at::Tensor>& blk_ws,
-                    const Descale& descale,
+                    const py::object& descale,
                     const c10::optional<at::Tensor>& alibi_slopes,
-                    int64_t alibi_offset, int64_t alibi_stride) {
+                    int64_t alibi_offset, int64_t alibi_stride,
+                    int64_t k_tile0) {
   fwd_accum_call(nullptr, q, k, v, softmax_scale, causal, acc, m, l, carry_in,
                  q_seg, kv_seg, band_lo, band_hi, softcap, block_mask,
-                 block_size, blk_ws, descale, alibi_slopes, alibi_offset,
-                 alibi_stride);
+                 block_size, blk_ws, descale_of(descale, k_tile0),
+                 alibi_slopes, alibi_offset, alibi_stride);
+}
+
+// x (fp16 / bf16 [B,S,H,128], strided) -> (x8 e4m3 contiguous, scale fp32):
+// mode "row" [B,H,S], "tile" [B,H,ceil(S/64)], "channel" [B,H,128].
+std::vector<at::Tensor> quantize_fp8(const at::Tensor& x,
+                                     const std::string& mode) {
+  check_qkv(x, "x");
+  const int m = mode == "row"       ? BAHIP_F8_QUANT_ROW
+                : mode == "tile"    ? BAHIP_F8_QUANT_TILE
+                : mode == "channel" ? BAHIP_F8_QUANT_CHANNEL
+                                    : -1;
+  TORCH_CHECK(m >= 0, "quantize_fp8: mode must be 'row', 'tile' or 'channel', "
+              "got '", mode, "'");
+  const auto B = x.size(0), S = x.size(1), H = x.size(2), D = x.size(3);
+  auto x8 = at::empty({B, S, H, D}, x.options().dtype(at::kFloat8_e4m3fn));
+  const int64_t last = m == BAHIP_F8_QUANT_ROW    ? S
+                       : m == BAHIP_F8_QUANT_TILE ? (S + 63) / 64
+                                                  : D;
+  auto scale = at::empty({B, H, last}, x.options().dtype(at::kFloat));
+  const int64_t bytes = bahip_attn_quantize_f8_workspace_bytes(m, B, S, H);
+  auto ws = at::empty({bytes > 0 ? bytes : 16}, x.options().dtype(at::kByte));
+  BA_CALL(bahip_attn_quantize_f8(
+      x.data_ptr(), x8.data_ptr(), scale.data_ptr<float>(), B, S, H, D,
+      Strides3(x), Strides3(x8), dtype_code(x), m, ws.data_ptr(), ws.numel(),
+      at::hip::getCurrentHIPStream().stream()));
+  return {x8, scale};
 }
 
 // The empty carry-in state ("no key seen yet") written into acc [B,S,N,D],
@@ -918,7 +1041,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("block_mask") = py::none(), py::arg("block_size") = 64,
         py::arg("blk_ws") = py::none(), py::arg("descale") = py::none(),
         py::arg("alibi_slopes") = py::none(), py::arg("alibi_offset") = 0,
-        py::arg("alibi_stride") = 1);
+        py::arg("alibi_stride") = 1, py::arg("k_tile0") = 0);
   m.def("attn_fwd_accum", &attn_fwd_accum,
         "carry-in accumulator fwd tile (in-kernel LSE merge)", py::arg("q"),
         py::arg("k"), py::arg("v"), py::arg("softmax_scale"),
@@ -929,7 +1052,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("block_mask") = py::none(), py::arg("block_size") = 64,
         py::arg("blk_ws") = py::none(), py::arg("descale") = py::none(),
         py::arg("alibi_slopes") = py::none(), py::arg("alibi_offset") = 0,
-        py::arg("alibi_stride") = 1);
+        py::arg("alibi_stride") = 1, py::arg("k_tile0") = 0);
+  m.def("quantize_fp8", &quantize_fp8,
+        "fp16 / bf16 [B,S,H,128] -> (e4m3, fp32 scale) per row, 64-row tile "
+        "or channel",
+        py::arg("x"), py::arg("mode"));
   m.def("attn_fp8_p_scale", [] { return (double)BAHIP_F8_P_SCALE; },
         "the power of two the fp8 forward multiplies P by before it rounds "
         "P to e4m3");

@@ -86,6 +86,21 @@ round hands the tile provider ``descale=``.  Inputs that require grad,
 and a malformed ``descale`` are refused before any round, and so is
 ``descale`` with 16-bit inputs, whose calls are otherwise unchanged.
 
+Block-scaled FP8: ``descale=(dq, dk, dv)`` may instead be three float32
+tensors on q's device, this rank's ``dq [B, N, S_local]`` (per token and head),
+``dk [B, Nk, ceil(S_local / 64)]`` (per 64-row tile and KV head) and
+``dv [B, Nk, 128]`` (per channel and KV head): what ``quantize_fp8(q, k, v)``
+returns for the rank's own shard, with no host sync and nothing all-reduced.
+``dq`` stays on the rank; ``dk`` and ``dv`` travel the ring with k and v as
+small float32 side payloads; every round hands the tile provider
+``descale=(dq[:, :, q_rows], the dk tiles of its k view, dv)``.  A k view must
+start on a multiple of 64 rows.  Both layouts' views start at row 0 (the whole
+chunk, the first zigzag half, or the striped chunk without its last row); the
+causal zigzag op also demands ``S_local % 128 == 0`` so that both half-chunks
+are whole tiles, and refuses anything else before any round.  Wrong shapes,
+dtypes or devices, a tensor that requires grad and a mix of floats and tensors
+are refused as a malformed ``descale`` is.
+
 ALiBi: the trailing keyword ``alibi_slopes`` (the flash-attn convention: an
 fp32 tensor ``[N]`` or ``[B, N]`` on q's device, one slope per *query* head)
 adds ``-slope[b, h] * |i - j|`` to the score of the query at GLOBAL position i
@@ -122,7 +137,8 @@ from .tile import get_tile_provider
 _logger = get_logger(__name__, level="WARN")
 
 __all__ = ["burst_attn_func", "burst_attn_func_striped", "OpBurstAttn",
-           "OpBurstAttnStrip", "window_tiles", "block_tiles", "alibi_tiles"]
+           "OpBurstAttnStrip", "window_tiles", "block_tiles", "alibi_tiles",
+           "quantize_fp8"]
 
 
 def get_partition_id(double_group, r, process_group=None):
@@ -592,8 +608,9 @@ _FP8 = torch.float8_e4m3fn
 
 
 def _check_fp8(q, k, v, descale, segment_ids, window, softcap, block_mask):
-    """None with 16-bit inputs, else the fp8 call's ``(sq, sk, sv)`` floats.
-    Everything an fp8 call cannot have is refused here, before any round."""
+    """None with 16-bit inputs, else the fp8 call's ``(sq, sk, sv)`` floats or
+    its ``(dq, dk, dv)`` scale tensors, contiguous.  Everything an fp8 call
+    cannot have is refused here, before any round."""
     dtypes = (q.dtype, k.dtype, v.dtype)
     if _FP8 not in dtypes:
         if descale is not None:
@@ -627,14 +644,57 @@ def _check_fp8(q, k, v, descale, segment_ids, window, softcap, block_mask):
         )
     if descale is None:
         return (1.0, 1.0, 1.0)
+    if (isinstance(descale, (tuple, list)) and len(descale) == 3
+            and all(isinstance(x, torch.Tensor) for x in descale)):
+        B, S, N, Nk = q.shape[0], q.shape[1], q.shape[2], k.shape[2]
+        want = ((B, N, S), (B, Nk, -(-S // 64)), (B, Nk, 128))
+        for name, t, shape in zip(("dq", "dk", "dv"), descale, want):
+            if (t.dtype != torch.float32 or tuple(t.shape) != shape
+                    or t.device != q.device or t.requires_grad):
+                raise ValueError(
+                    "descale must be (dq, dk, dv) float32 tensors on q's "
+                    "device that do not require grad, dq [B, N, S], dk [B, "
+                    f"Nk, ceil(S / 64)], dv [B, Nk, 128]: {name} must be "
+                    f"{shape}, got {tuple(t.shape)} of {t.dtype} on "
+                    f"{t.device}"
+                    + (" that requires grad" if t.requires_grad else "")
+                )
+        return tuple(t.contiguous() for t in descale)
     if (not isinstance(descale, (tuple, list)) or len(descale) != 3
             or any(isinstance(x, bool) or not isinstance(x, (int, float))
                    or not math.isfinite(x) or x <= 0 for x in descale)):
         raise ValueError(
             "descale must be (sq, sk, sv), three positive finite Python "
-            f"floats, got {descale!r}"
+            "floats, or (dq, dk, dv), three float32 tensors (never a mix), "
+            f"got {descale!r}"
         )
     return tuple(float(x) for x in descale)
+
+
+def _dk_tiles(dk, kv_rows, s_local, layout):
+    """The ``dk`` entries of the k view ``kv_rows`` of a rank's ``s_local``
+    rows: one per 64-row tile, so the view must start on a tile."""
+    start, stop, _ = kv_rows.indices(s_local)
+    if start % 64:
+        raise ValueError(
+            f"descale tensors: the {layout} layout hands the tile kernel a k "
+            f"view that starts at row {start}, not a multiple of 64"
+        )
+    return dk[:, :, start // 64:-(-stop // 64)]
+
+
+def quantize_fp8(q, k, v):
+    """fp16 / bf16 q ``[B, S, N, 128]`` and k, v ``[B, S, Nk, 128]`` ->
+    ``(q8, k8, v8, (dq, dk, dv))`` for ``burst_attn_func(..., descale=(dq, dk,
+    dv))``: ``torch.float8_e4m3fn`` tensors and their fp32 scales, q per token
+    and head, k per 64-row tile and head, v per channel and head of this rank's
+    rows.  Three HIP kernels, no host sync, nothing all-reduced: every rank
+    quantises its own shard and ``dk``, ``dv`` travel the ring with k and v."""
+    P = get_tile_provider()
+    (q8, dq), (k8, dk), (v8, dv) = (
+        P.quantize_fp8(t, mode)
+        for t, mode in ((q, "row"), (k, "tile"), (v, "channel")))
+    return q8, k8, v8, (dq, dk, dv)
 
 
 def _op_args(ids, window, softcap, blocks=None, descale=None, alibi=None):
@@ -756,10 +816,20 @@ def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
     ctx.window = window
     ctx.softcap = softcap
     cap = {"softcap": softcap} if softcap > 0 else {}
+    scales = None  # (dq, dk, dv) of a block-scaled fp8 call
     if descale is not None:
         cap = {"descale": descale}  # never together with a softcap
         # the wire carries bytes: RCCL and gloo need no fp8 support
         k, v = k.view(torch.uint8), v.view(torch.uint8)
+        if isinstance(descale[0], torch.Tensor):
+            scales, cap = descale, {}
+            if layout == "zigzag" and causal and q.shape[1] % 128:
+                raise ValueError(
+                    "descale tensors: the zigzag layout needs a per-rank "
+                    f"seqlen that is a multiple of 128, got {q.shape[1]} "
+                    "(dk is one scale per 64 k rows, and both half-chunks "
+                    "must be whole tiles)"
+                )
     ctx.dq_group = double_group
     if isinstance(double_group[0], tuple):
         # [(group, dq_group), (group2, dq_group2)] — separate backward dq
@@ -785,6 +855,9 @@ def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
     if ids is not None:
         kv_ids = replicate(ids)
         comm_bufs.append(torch.empty_like(ids))
+    if scales is not None:  # dq stays; dk and dv travel with k and v
+        dq_s, dk_s, dv_s = scales
+        comm_bufs += [torch.empty_like(dk_s), torch.empty_like(dv_s)]
     state = None  # provider-owned carry-in accumulator (in-kernel merge)
     if window is not None:
         state = P.fwd_empty_state(q)
@@ -810,6 +883,8 @@ def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
         if window is None and block_mask is None and alibi is None:
             qw, kw, tile_causal = tile_window(layout, rank, src, causal, q.shape[1])
         payload = [k, v] if ids is None else [k, v, kv_ids]
+        if scales is not None:
+            payload += [dk_s, dv_s]
         if r != W:
             ring.double_ring_send_recv(payload, comm_bufs, r)
             ring.commit()
@@ -841,6 +916,10 @@ def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
             kt, vt = k[:, kw], v[:, kw]
             if descale is not None:
                 kt, vt = kt.view(_FP8), vt.view(_FP8)
+            if scales is not None:
+                cap = {"descale": (dq_s[:, :, qw],
+                                   _dk_tiles(dk_s, kw, k.shape[1], layout),
+                                   dv_s)}
             state = P.fwd_accum(state, q[:, qw], kt, vt, scale,
                                 tile_causal, row_offset=qw.start or 0, **seg,
                                 **cap)
@@ -849,6 +928,8 @@ def _ring_forward(layout, ctx, q, k, v, softmax_scale=None, flash="cuda",
             k, v = recv[:2]
             if ids is not None:
                 kv_ids = recv[2]
+            if scales is not None:
+                dk_s, dv_s = recv[2:4]
             ring.wait()
     _logger.info("fwd record of rank %d: %s", get_rank(), record)
     # o in q.dtype, lse [B,N,S] fp32 (reference :250-252 semantics)

@@ -106,6 +106,19 @@ unchanged.  There is no backward; ``seg``, ``band``, ``softcap`` and
 ``blocks`` with fp8 are refused.  A caller without fp8 inputs passes no
 ``descale`` keyword at all.
 
+Block-scaled FP8: ``descale=(dq, dk, dv)`` may instead be three fp32 tensors
+on q's device with a contiguous last dim, ``dq [B, N, Sq]`` (one per q row and
+head), ``dk [B, Nk, ceil(Sk / 64)]`` (one per 64-row tile of the k passed and
+KV head) and ``dv [B, Nk, 128]`` (one per v channel and KV head): real values
+``q8 * dq[row]``, ``k8 * dk[tile]``, ``v8 * dv[channel]``, read by the kernel on
+the device.  They describe the rows actually passed: the caller slices them as
+it slices ``seg``, so a k view starts on a multiple of 64 rows of the tensor
+that was quantised.  Views are handed over by their strides.  The state stays
+fp32 in real units, so rounds with different scales merge.  A mix of floats
+and tensors is refused.  ``quantize_fp8(x, mode)`` (``"row"``, ``"tile"``,
+``"channel"``) is the HIP quantiser that produces ``(x8, scale)`` from fp16 or
+bf16 ``[B, S, H, 128]``.
+
 ALiBi: ``fwd``, ``fwd_accum``, ``bwd`` and ``bwd_accum`` take an optional
 keyword ``alibi=(slopes, offset, stride)``: an fp32 tensor ``[1 or B, N]``,
 contiguous, on q's device, with one slope per *query* head, and two Python
@@ -250,6 +263,12 @@ class HipTileProvider:
                 raise RuntimeError(
                     f"fp8 inputs do not support {name} (plain calls only)")
         sq, sk, sv = (1.0, 1.0, 1.0) if descale is None else descale
+        tensors = [isinstance(x, torch.Tensor) for x in (sq, sk, sv)]
+        if all(tensors):  # the block-scaled kernel reads them on the device
+            return {"descale": (sq, sk, sv)}
+        if any(tensors):
+            raise RuntimeError(
+                "descale must be three floats or three tensors, not a mix")
         return {"descale": (float(sq), float(sk), float(sv))}
 
     def fwd(self, q, k, v, scale, causal, seg=None, band=None, softcap=None,
@@ -355,6 +374,11 @@ class HipTileProvider:
         accv, mv, lv = acc[:, sl], m[:, :, sl], l[:, :, sl]
         accum(q, k, v, float(scale), bool(causal), accv, mv, lv, True)
         return state
+
+    def quantize_fp8(self, x, mode):
+        """fp16 / bf16 ``[B, S, H, 128]`` -> ``(x8, scale)``: e4m3 and the
+        fp32 scales per ``"row"``, 64-row ``"tile"`` or ``"channel"``."""
+        return tuple(self._ext.quantize_fp8(x, mode))
 
     def fwd_empty_state(self, q, v_dim=None):
         """The state of "no key seen yet" over q's [B, S, N, D] rows; the

@@ -188,6 +188,27 @@
  *     BAHIP_ERR_UNSUPPORTED naming what was asked.  Nothing is launched by a
  *     refused call.  There is no backward and no mask form.  Every other
  *     entry point keeps refusing BAHIP_F8E4M3 as an unknown dtype code.
+ *   - Block-scaled FP8: the *_f8_scaled entry points are the *_f8 ones with
+ *     the descales read from device memory, so that no value has to come back
+ *     to the host: real values are q8 * descale_q[b][n][row], k8 *
+ *     descale_k[b][n / G][k_tile0 + kv_row / 64] and v8 *
+ *     descale_v[b][n / G][channel].  The tensors are fp32 with innermost
+ *     stride 1 and {batch, head} element strides of their own, so slices of
+ *     larger tensors are legal; descale_q and descale_v describe exactly the
+ *     rows and channels passed, descale_k the 64-row tiles of k counted from
+ *     k_tile0 (a k view therefore starts on a tile of the tensor that was
+ *     quantised).  Every entry must be positive and finite: they live on the
+ *     device and are not checked.  A null tensor or strides pointer, or a
+ *     negative k_tile0, returns BAHIP_ERR_DESCALE; everything *_f8 refuses is
+ *     refused alike, and nothing is launched by a refused call.  Outputs, the
+ *     state contract and the workspace are those of *_f8.  The per-tensor
+ *     entry points launch the kernels they launched before.
+ *     bahip_attn_quantize_f8 produces such inputs from fp16 / bf16 at D = 128:
+ *     x8 = round-to-nearest-even(x / scale) with scale = amax / 448 of the
+ *     element's group (never below FLT_MIN, 1.0 for an all-zero group), in the
+ *     three groupings above.  Misaligned bases or strides, another D, dtype
+ *     or mode return BAHIP_ERR_UNSUPPORTED, a null tensor BAHIP_ERR_DESCALE, a
+ *     short channel-mode workspace BAHIP_ERR_WORKSPACE.
  *   - ALiBi (the flash-attn `alibi_slopes` argument): the *_alibi entry
  *     points take, before stream, slopes (fp32, one per QUERY head, head
  *     stride 1), slopes_batch_stride (elements between batch rows, 0 = one row
@@ -254,7 +275,7 @@ extern "C" {
                                          not in {1, Nk} */
 
 #define BAHIP_ERR_DESCALE 1010        /* an fp8 descale not positive or not
-                                         finite */
+                                         finite, or a null descale tensor */
 
 #define BAHIP_ERR_ALIBI 1011          /* pos_stride < 1, or a position
                                          distance beyond 2^30 */
@@ -686,6 +707,55 @@ int bahip_attn_fwd_accum_f8(
     float* acc, float* m, float* l, const int64_t acc_strides[3],
     const int64_t ml_strides[2], int carry_in,
     float descale_q, float descale_k, float descale_v,
+    void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- block-scaled FP8 forward and its quantiser (see "Block-scaled FP8") ----
+ * The *_f8 argument lists with the three floats replaced by three fp32 device
+ * tensors (innermost stride 1), their {batch, head} element strides and
+ * k_tile0, the descale_k index of the call's first 64-row kv tile:
+ *   descale_q [B][N][Sq], descale_k [B][Nk][>= k_tile0 + ceil(Sk/64)],
+ *   descale_v [B][Nk][128]. */
+int bahip_attn_fwd_f8_scaled(
+    const void* q, const void* k, const void* v,
+    float* o, float* lse,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3],
+    const int64_t k_strides[3],
+    const int64_t v_strides[3],
+    float softmax_scale, int causal, int dtype,
+    const float* descale_q, const float* descale_k, const float* descale_v,
+    const int64_t dq_strides[2], const int64_t dk_strides[2],
+    const int64_t dv_strides[2], int64_t k_tile0,
+    void* workspace, int64_t workspace_bytes, void* stream);
+int bahip_attn_fwd_accum_f8_scaled(
+    void* hip_function,
+    const void* q, const void* k, const void* v,
+    int64_t B, int64_t Sq, int64_t Sk, int64_t N, int64_t Nk, int64_t D,
+    const int64_t q_strides[3], const int64_t k_strides[3],
+    const int64_t v_strides[3], float softmax_scale, int causal, int dtype,
+    float* acc, float* m, float* l, const int64_t acc_strides[3],
+    const int64_t ml_strides[2], int carry_in,
+    const float* descale_q, const float* descale_k, const float* descale_v,
+    const int64_t dq_strides[2], const int64_t dk_strides[2],
+    const int64_t dv_strides[2], int64_t k_tile0,
+    void* workspace, int64_t workspace_bytes, void* stream);
+
+/* x (fp16 / bf16 [B][S][H][128], element strides {b, s, h}) -> x8 (e4m3
+ * bytes, byte strides {b, s, h}) and `scale`, contiguous fp32:
+ *   BAHIP_F8_QUANT_ROW      [B][H][S]             one per row (q)
+ *   BAHIP_F8_QUANT_TILE     [B][H][ceil(S/64)]    one per 64-row tile (k)
+ *   BAHIP_F8_QUANT_CHANNEL  [B][H][128]           one per channel (v)
+ * Only the channel mode needs a workspace. */
+#define BAHIP_F8_QUANT_ROW 0
+#define BAHIP_F8_QUANT_TILE 1
+#define BAHIP_F8_QUANT_CHANNEL 2
+int64_t bahip_attn_quantize_f8_workspace_bytes(int mode, int64_t B, int64_t S,
+                                               int64_t H);
+int bahip_attn_quantize_f8(
+    const void* x, void* x8, float* scale,
+    int64_t B, int64_t S, int64_t H, int64_t D,
+    const int64_t x_strides[3], const int64_t x8_strides[3],
+    int dtype, int mode,
     void* workspace, int64_t workspace_bytes, void* stream);
 
 /* The empty state, "no key seen yet", over [B, S] rows of a carry-in state
