@@ -66,13 +66,14 @@ def tile_fwd(q, k, v, softmax_scale=None, causal=False, q_block=512, k_block=512
         (that epsilon exists only on the math path);
       * o is returned normalised, in fp32 (caller casts).
 
-    Returns (o [B,S,N,D] fp32, lse [B,N,S] fp32).
+    Returns (o [B,S,N,Dv] fp32, lse [B,N,S] fp32); o takes its width from
+    v, which may differ from q's and k's.
     """
     if softmax_scale is None:
         softmax_scale = 1.0 / math.sqrt(q.shape[-1])
     qf, kf, vf = _as_f32_bnsd(q), _as_f32_bnsd(k), _as_f32_bnsd(v)
-    B, N, Sq, D = qf.shape
-    Sk = kf.shape[2]
+    B, N, Sq, _ = qf.shape
+    Sk, D = kf.shape[2], vf.shape[3]
     if causal:
         assert Sq == Sk, "causal tiles are equal-length in this codebase"
     o = torch.zeros(B, N, Sq, D, dtype=torch.float32)

@@ -39,6 +39,11 @@ __all__ = [
     "DOMINATED_MIN_GAP",
     "DOMINATED_CASES",
     "dominated_kv",
+    "BLOCK_SEAMS",
+    "SET_CASES",
+    "SET_DOMINATED_CASES",
+    "v_dim",
+    "kernel_set",
     "case_id",
     "dtype_name",
     "K_POISON",
@@ -60,16 +65,22 @@ V_POISON = 1.0e4  # V and dO rows (finite in fp16)
 SENTINEL = -12345.0  # fp32 output parents
 
 
-def seam_keys(sk):
+# the head_dim 256 and 192/128 kernel sets own 128 rows per workgroup
+BLOCK_SEAMS = (127, 128)
+
+
+def seam_keys(sk, extra=()):
     """Key positions on the kernels' seams: the 32-row subtile, the 64-row
-    kv tile, the 256-row workgroup and the ragged tail."""
-    return sorted({j for j in (0, 31, 32, 63, 64, 255, 256, sk - 2, sk - 1)
+    kv tile, the 256-row workgroup and the ragged tail; `extra` adds the
+    seams of another kernel set (BLOCK_SEAMS)."""
+    return sorted({j for j in (0, 31, 32, 63, 64, 255, 256, sk - 2, sk - 1,
+                               *extra)
                    if 0 <= j < sk})
 
 
-def seam_rows(sq):
+def seam_rows(sq, extra=()):
     """Query rows on the wave (32), workgroup (256) and tail seams."""
-    return sorted({i for i in (0, 31, 32, 255, 256, sq - 2, sq - 1)
+    return sorted({i for i in (0, 31, 32, 255, 256, sq - 2, sq - 1, *extra)
                    if 0 <= i < sq})
 
 
@@ -85,7 +96,8 @@ def _randn(g, *shape):
     return torch.randn(*shape, generator=g)
 
 
-def seam_weighted(b, sq, sk, n, nk, d, dtype, seed, beta=None, gain=DO_GAIN):
+def seam_weighted(b, sq, sk, n, nk, d, dtype, seed, beta=None, gain=DO_GAIN,
+                  dv=None, extra=()):
     """randn q/k/v/do with q += u and k[J] += (beta / sqrt(d)) u.
 
     u.u = d, so each key of J = seam_keys(sk) gains +beta in scaled score
@@ -96,19 +108,23 @@ def seam_weighted(b, sq, sk, n, nk, d, dtype, seed, beta=None, gain=DO_GAIN):
     all rows at once (the last row's diagonal key then moved o by only
     1.25 bf16 gates when dropped; without it by 4.4).  do is multiplied by
     `gain` on seam_rows(sq).  Returns (q, k, v, do).
+
+    `dv` is the width of v and do where it differs from d; `extra` keys
+    and rows are seams too (BLOCK_SEAMS for the 128-row kernel sets).
     """
     if beta is None:
         beta = math.log(max(sk, 2))
+    dv = d if dv is None else dv
     g = torch.Generator().manual_seed(seed)
     u = seam_vector(d)
     q = _randn(g, b, sq, n, d)
     k = _randn(g, b, sk, nk, d)
     k -= (k @ u / d).unsqueeze(-1) * u
-    v = _randn(g, b, sk, nk, d)
-    do = _randn(g, b, sq, n, d)
+    v = _randn(g, b, sk, nk, dv)
+    do = _randn(g, b, sq, n, dv)
     q += u
-    k[:, seam_keys(sk)] += (beta / math.sqrt(d)) * u
-    do[:, seam_rows(sq)] *= gain
+    k[:, seam_keys(sk, extra)] += (beta / math.sqrt(d)) * u
+    do[:, seam_rows(sq, extra)] *= gain
     return tuple(t.to(dtype) for t in (q, k, v, do))
 
 
@@ -126,7 +142,7 @@ def _rows_from(t, shift):
     return out
 
 
-def diag_needle(b, s, n, nk, d, dtype, seed, a=None, c=None, lag=0):
+def diag_needle(b, s, n, nk, d, dtype, seed, a=None, c=None, lag=0, dv=None):
     """Causal family: k_j = eps_j + a q_j / sqrt(d) + c q_{j-1} / sqrt(d).
 
     q rows are normalised to |q|^2 = d, so score(i, i) = a and
@@ -142,8 +158,10 @@ def diag_needle(b, s, n, nk, d, dtype, seed, a=None, c=None, lag=0):
     rows outside the sequence contributing zero.  Chunked over W ring ranks
     those keys belong to another rank: they are the boundary pairs of the
     ring's cross-rank tiles (tests/ring_rounds.py).  lag = 0 is the family
-    above, bit for bit.
+    above, bit for bit.  `dv` is the width of v and do where it differs
+    from d.
     """
+    dv = d if dv is None else dv
     if a is None:
         a = math.log(max(s, 2))
     if c is None:
@@ -152,8 +170,8 @@ def diag_needle(b, s, n, nk, d, dtype, seed, a=None, c=None, lag=0):
     q = _randn(g, b, s, n, d)
     q = q * (math.sqrt(d) / q.norm(dim=-1, keepdim=True))
     eps = _randn(g, b, s, nk, d)
-    v = _randn(g, b, s, nk, d)
-    do = _randn(g, b, s, n, d)
+    v = _randn(g, b, s, nk, dv)
+    do = _randn(g, b, s, n, dv)
     qh = q[:, :, :: n // nk]  # the group's first query head, [B,S,Nk,D]
     q_hot = _rows_from(qh, lag)
     q_prev = _rows_from(qh, -max(lag, 1))
@@ -228,7 +246,8 @@ def view_of(parent, like_view, like_parent):
 # ---- the shapes the boundary tests run, shared by the GPU tests and the
 # CPU sensitivity proof so that the proof covers exactly what runs
 
-Case = namedtuple("Case", "family b sq sk n nk d causal")
+# dv: the width of v, do, o and dv where it differs from d (192 / 128)
+Case = namedtuple("Case", "family b sq sk n nk d causal dv", defaults=(None,))
 
 _CAUSAL_S = (328,  # two 256-row workgroups and a ragged 72 = 64 + 8 tail
              296,  # five kv tiles: NBUF=4 wraps
@@ -256,16 +275,67 @@ KNOB_CASES = [c for c in CASES if c.sq == 328
               and (c.family == "diag_needle") == c.causal]
 
 
+# ---- the same forms at the shapes of the 128-row kernel sets: head_dim
+# 256 and 192 / 128 (tests/test_gpu_boundary_sets.py).  Below one block,
+# one row past it, and the 328 = 2 x 128 + 64 + 8 of their own tests.
+_SET_CAUSAL_S = (1, 33, 129, 328)
+_SET_NONCAUSAL_SQ_SK = ((40, 1), (40, 33), (40, 65), (129, 127), (96, 320),
+                        (328, 328))
+
+
+def _set_cases():
+    out = []
+    for d, dv in ((256, None), (192, 128)):
+        for n, nk in ((4, 2), (2, 2)):
+            for s in _SET_CAUSAL_S:
+                if (n, nk) == (2, 2) and s != 328:
+                    continue
+                out.append(Case("seam_weighted", 2, s, s, n, nk, d, True, dv))
+                out.append(Case("diag_needle", 2, s, s, n, nk, d, True, dv))
+            for sq, sk in _SET_NONCAUSAL_SQ_SK:
+                if (n, nk) == (2, 2) and (sq, sk) != (328, 328):
+                    continue
+                out.append(Case("seam_weighted", 2, sq, sk, n, nk, d, False,
+                                dv))
+    return out
+
+
+SET_CASES = _set_cases()
+
+
+def v_dim(case):
+    return case.d if case.dv is None else case.dv
+
+
+def kernel_set(case):
+    """Which kernel set serves the case's widths."""
+    return {(256, 256): "d256", (192, 128): "hd192"}.get(
+        (case.d, v_dim(case)), "plain")
+
+
+def _extra_seams(case):
+    return BLOCK_SEAMS if kernel_set(case) != "plain" else ()
+
+
 def make_inputs(case, dtype, seed_offset=0):
     """(q, k, v, do) of a Case; seeded by the case, so every test that
-    names the same case sees the same tensors."""
+    names the same case sees the same tensors.  Cases of the 128-row
+    kernel sets carry BLOCK_SEAMS keys and rows too."""
     seed = (4242 + 11 * case.sq + 5 * case.sk + 3 * case.n + case.nk
             + case.d + seed_offset)
+    if kernel_set(case) != "plain":
+        # a draw of their own: with the offset-free seed the 328 x 328
+        # n2k2 d192 draw put full_subtile_early's forward at 2.93 fp16
+        # gates (3.3 .. 7.5 at this and every other seed tried); see
+        # tests/test_gate_sensitivity_sets_cpu.py
+        seed += 1000
     if case.family == "seam_weighted":
         return seam_weighted(case.b, case.sq, case.sk, case.n, case.nk,
-                             case.d, dtype, seed)
+                             case.d, dtype, seed, dv=case.dv,
+                             extra=_extra_seams(case))
     assert case.family == "diag_needle" and case.causal
-    return diag_needle(case.b, case.sq, case.n, case.nk, case.d, dtype, seed)
+    return diag_needle(case.b, case.sq, case.n, case.nk, case.d, dtype, seed,
+                       dv=case.dv)
 
 
 ROUND2_BETA_DROP = 2.5
@@ -286,7 +356,8 @@ def round2_kv(case, dtype):
     beta = math.log(max(case.sk, 2)) - ROUND2_BETA_DROP
     _, k, v, _ = seam_weighted(case.b, case.sq, case.sk, case.n, case.nk,
                                case.d, dtype, 9001 + case.sk + case.d,
-                               beta=beta)
+                               beta=beta, dv=case.dv,
+                               extra=_extra_seams(case))
     return k, v
 
 
@@ -295,13 +366,17 @@ def round2_kv(case, dtype):
 # the state carries.  A key's score moves by gain (1 + z / sqrt(d)), z ~
 # N(0, 1) from q's own component along u (|z| reaches 3.5 over the rows);
 # 80 leaves every second-round score of a row at least 30 from the row's
-# carried max at d = 64 and 128 (tests/test_boundary_inputs_cpu.py), and at
-# most 130: exp2(-130 log2 e) is 0 in fp32, the carried side must vanish.
+# carried max at d = 64, 128, 192 and 256
+# (tests/test_boundary_inputs_cpu.py), and at most 130: exp2(-130 log2 e) is
+# 0 in fp32, the carried side must vanish.
 DOMINATED_GAIN = 80.0
 DOMINATED_MIN_GAP = 30.0
 DOMINATED_CASES = [c for c in CASES
                    if c.family == "seam_weighted" and c.causal
                    and c.sq == 328 and (c.n, c.nk) == (4, 2)]
+SET_DOMINATED_CASES = [c for c in SET_CASES
+                       if c.family == "seam_weighted" and c.causal
+                       and c.sq == 328 and (c.n, c.nk) == (4, 2)]
 
 
 def dominated_kv(case, dtype, which):

@@ -121,7 +121,7 @@ def merged_bwd_ref(case, dtype):
         softmax_d=delta[:, :, 1:])
     dq[:, 1:] += dq2
     pad = lambda g: torch.cat(
-        [reduce_kv_grad(g, nk), torch.zeros(case.b, 1, nk, case.d)], 1)
+        [reduce_kv_grad(g, nk), torch.zeros(case.b, 1, nk, g.shape[3])], 1)
     return (dq, reduce_kv_grad(dk, nk), reduce_kv_grad(dv, nk), pad(dk2),
             pad(dv2))
 

@@ -86,7 +86,8 @@ def forward(q, k, v, scale, spec, round_dtype=None):
 
 
 def backward(do, q, k, v, o, lse, scale, spec, round_dtype=None):
-    """(dq [B,Sq,N,D], dk, dv [B,Sk,Nk,D]) fp32: oracle.tile_bwd's math,
+    """(dq [B,Sq,N,D], dk [B,Sk,Nk,D], dv [B,Sk,Nk,Dv]) fp32:
+    oracle.tile_bwd's math,
         p = exp(s - lse); dv += p^T do; ds = p (do v^T - delta) scale;
         dq = ds k; dk += ds^T q,
     with delta = rowsum(o * do)."""
@@ -104,7 +105,7 @@ def backward(do, q, k, v, o, lse, scale, spec, round_dtype=None):
     dk_h = torch.matmul((ds_r * spec.kv_weight).transpose(-2, -1), qf)
     sk, nk = k.shape[1], k.shape[2]
     dk = torch.zeros(k.shape[0], nk, sk, k.shape[3])
-    dv = torch.zeros_like(dk)
+    dv = torch.zeros(k.shape[0], nk, sk, v.shape[3])
     for h, kvh in enumerate(spec.head_map):
         # a duplicated tail key has no row of its own to land in
         dk[:, kvh] += dk_h[:, h, :sk]
@@ -250,6 +251,49 @@ MUTANTS = [
            "kp = k + b * k_sb with a zero batch stride: attn_fwd.hip:140, "
            "attn_bwd.hip:112 and :362",
            ("fwd", "bwd"), _batch1_reads_batch0_k),
+]
+
+
+# The same three workgroup-seam errors for the kernel sets that own 128 rows
+# per workgroup (head_dim 256, 192 / 128): the seam is row 128, not 256.
+
+def _block128_subtile_early(spec, c):
+    if not c.causal:
+        return None
+    m = _copy(spec)
+    m.allow[128:160, 128:160] = True
+    return m
+
+
+def _block128_last_tile_skipped(spec, c):
+    if not c.causal:
+        return None
+    m = _copy(spec)
+    m.allow[96:128, 64:128] = False
+    return m
+
+
+def _block128_bwd_t0_late(spec, c):
+    if not c.causal:
+        return None
+    m = _copy(spec)
+    m.kv_weight[128:160, 128:] = 0.0
+    return m
+
+
+BLOCK128_MUTANTS = [
+    Mutant("block128_subtile_early",
+           "the diagonal 32x32 subtile at row 128, the first of the second "
+           "128-row block, taken as full: attn_d256_fwd.hip:183",
+           ("fwd",), _block128_subtile_early),
+    Mutant("block128_last_tile_skipped",
+           "kv_limit = (blockIdx.x + 1) * BA_D256_BLOCK one 64-row tile "
+           "short: attn_d256_fwd.hip:110 (rows 96..127 lose keys 64..127)",
+           ("fwd", "bwd"), _block128_last_tile_skipped),
+    Mutant("block128_bwd_t0_late",
+           "the dk/dv pass of the second 128-row block starting one q tile "
+           "late (q rows 128..159 missing from dk/dv of keys >= 128)",
+           ("bwd",), _block128_bwd_t0_late),
 ]
 
 

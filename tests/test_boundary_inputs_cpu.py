@@ -85,10 +85,12 @@ def test_diag_needle_lag_scores(lag):
 @pytest.mark.parametrize("which", ["below", "above"])
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16],
                          ids=bi.dtype_name)
-@pytest.mark.parametrize("case", bi.DOMINATED_CASES, ids=bi.case_id)
+@pytest.mark.parametrize("case", bi.DOMINATED_CASES + bi.SET_DOMINATED_CASES,
+                         ids=bi.case_id)
 def test_dominated_round_gap(case, dtype, which):
     """Every score of the dominated causal round is at least 30 from the
-    row's carried max, on the side asked for."""
+    row's carried max, on the side asked for, and at most 130 from it; at
+    head_dim 256 and 192 as at 64 and 128."""
     q, k, _, _ = _inputs(case, dtype)
     k2, _ = bi.dominated_kv(case, dtype, which)
     tril = torch.ones(case.sq, case.sk, dtype=torch.bool).tril()
@@ -134,7 +136,10 @@ def test_poisoned_parent_geometry():
 
 @pytest.mark.parametrize(
     "case", [c for c in bi.CASES if c.causal and c.n == 4 and c.d == 64
-             and c.sq in (33, 328)],
+             and c.sq in (33, 328)]
+    # v narrower than q and k: the references take o's width from v
+    + [c for c in bi.SET_CASES if c.causal and c.n == 4 and c.d == 192
+       and c.sq == 33],
     ids=bi.case_id)
 def test_shifted_references_are_masked_eager(case):
     """shifted_ref and merged_bwd_ref against the eager softmax and its

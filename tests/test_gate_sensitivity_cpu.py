@@ -209,11 +209,12 @@ def _ctx(case):
 
 
 @functools.lru_cache(maxsize=None)
-def evaluate(case, dtype, randn=False):
+def evaluate(case, dtype, randn=False, block128=False):
     """{"emu": {output: ratio}, (mutant, stage): {output: ratio}} for one
     case: the fp32 math against itself with one predicate changed, and
     against its rounding emulation.  randn=True swaps the family's inputs
-    for plain randn ones (the control)."""
+    for plain randn ones (the control); block128=True adds
+    mo.BLOCK128_MUTANTS."""
     if randn:
         g = torch.Generator().manual_seed(7)
         mk = lambda s, h: torch.randn(case.b, s, h, case.d,
@@ -285,7 +286,7 @@ def evaluate(case, dtype, randn=False):
         ref_s = shifted(base, base2)
         out["emu_shift"] = _ratios(shifted(base, base2, dtype), ref_s, dtype,
                                    grp)
-    for mut in mo.MUTANTS:
+    for mut in mo.MUTANTS + (mo.BLOCK128_MUTANTS if block128 else []):
         if shifted_form and "fwd" in mut.stages:
             spec1, spec2 = mo.mutate(mut, ctx), mo.mutate(mut, ctx2)
             if spec1 is not None or spec2 is not None:

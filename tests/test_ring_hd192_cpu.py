@@ -2,7 +2,7 @@
 
 The ring carries k and v as separate tensors and sizes every o-shaped buffer
 by what it is handed, so with a two-width tile provider injected (fp32 math
-of its own; ``oracle.tile_fwd`` sizes o by q's width) the zigzag and striped
+of its own, independent of ``oracle.tile_fwd``) the zigzag and striped
 rings at W = 2 and the 2 x 2 double ring match eager fp64 attention.  Also
 pins what the interface refuses for this shape before any round, and that
 any other pair of differing widths keeps its message.

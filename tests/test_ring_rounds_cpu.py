@@ -3,7 +3,8 @@ on its cases the parity gates see an error confined to one ring seam.
 
 (a) ``ring_rounds.replay_ring`` with the oracle tile provider on fp32
     inputs equals full-sequence eager attention, at W = 1..4, both
-    layouts, causal and not, equal and grouped heads.
+    layouts, causal and not, equal and grouped heads; also with v, do, o
+    and dv narrower than q and k.
 
 (b) Sensitivity, in the manner of tests/test_gate_sensitivity_cpu.py and
     with its CAUGHT / CLEAN: on every case of ``ring_rounds.CASES`` and
@@ -91,6 +92,28 @@ def test_replay_equals_full_sequence(W, layout, causal, n, nk):
     for out, ref in ((o, o_r), (lse, lse_r), (dq, dq_r), (dk, dk_r),
                      (dv, dv_r)):
         torch.testing.assert_close(out, ref, **tol)
+
+
+@pytest.mark.parametrize("causal", [True, False], ids=["causal", "full"])
+@pytest.mark.parametrize("layout", ["zigzag", "striped"])
+@pytest.mark.parametrize("W", [1, 3, 4])
+def test_replay_equals_full_sequence_narrow_v(W, layout, causal):
+    """v, do, o and dv narrower than q and k (the 192 / 128 heads): dv takes
+    v's shape, dk k's."""
+    b, s_local, n, nk, d, dv_ = 2, 10, 4, 2, 24, 16
+    S = W * s_local
+    g = torch.Generator().manual_seed(57 * W)
+    q, k = (torch.randn(b, S, h, d, generator=g) for h in (n, nk))
+    v, do = (torch.randn(b, S, h, dv_, generator=g) for h in (nk, n))
+    scale = d ** -0.5
+    got = rr.replay_ring(GqaOracleTileProvider(), q, k, v, do, W, scale,
+                         causal, layout)
+    o_r, dq_r, dk_r, dv_r = gqa_full_reference(q, k, v, do, scale, causal)
+    lse_r = mo.forward(q, k, v, scale, mo.base_spec(
+        mo.Ctx(b, S, S, n, nk, causal)))[1]
+    for out, ref in zip(got, (o_r, lse_r, dq_r, dk_r, dv_r)):
+        assert out.shape == ref.shape
+        torch.testing.assert_close(out, ref, rtol=1e-4, atol=1e-4)
 
 
 # ---- (b) window mutants: tile_window with one rank relation changed
